@@ -3,7 +3,8 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model zipformer-68m]
                     [--method greedy_search|modified_beam_search] [--beam 8]
                     [--hotwords-file default|PATH] [--audio-sec 3600]
-                    [--precision bf16|bf16_enc|fp32] [--no-cpu-baseline] [--shape-table]
+                    [--precision bf16|bf16_enc|fp32] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--shape-table]]
 
 One step = one pass of the hot path (fbank -> Conv2dSubsampling -> Zipformer2 encoder ->
 decoder/joiner -> search) over one batch: `--audio-sec` seconds (default 1 h) of seeded
@@ -18,7 +19,13 @@ the GPU) and exits with its return code.  Under torch.distributed each rank deco
 hour (seed + rank; weak scaling, no collective on the data path); the timed region is
 bracketed by barriers and the time is the max over ranks.
 
-Prints one JSON line (rank 0).  DESIGN.md §7 has the roofline accounting.
+Prints one JSON line (rank 0).  A plain run does only what the headline figure needs: set-up,
+warm-up, the K timed steps, the line.  --full adds every side measurement to the same line (CPU
+baseline, single-batch latency, kernel-class profile and rooflines, oracle agreement, the run
+from host audio, the token-exact parity mode and the config 3 / 4 / 5 lines in child
+processes); DESIGN.md §7 has the roofline accounting.  --dump-outputs DIR writes what the last
+timed step returned as DIR/<name>.npy (the inputs are seeded, so two builds compare output for
+output).
 """
 from __future__ import annotations
 
@@ -62,6 +69,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks that are not part of the "
+                         "headline figure: CPU baselines (every stage), and for the asr stage the "
+                         "single-batch latency, the kernel-class profile with its rooflines "
+                         "(--shape-table), the oracle agreement, the host-audio run, the parity "
+                         "mode and the config 3 / 4 / 5 lines (child processes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32 / float64; rank 0)")
     ap.add_argument("--model", default="zipformer-68m")
     ap.add_argument("--method", default="greedy_search")
     ap.add_argument("--beam", type=int, default=8)
@@ -147,6 +163,8 @@ def parse_args(argv=None):
                     help="CAM++ windows per launch group (the reference batches 32 on CPU; "
                          "measured 512 -> 6000: 167 -> 123 ms per hour, profiles/r02/campp_batch)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.proxy_ranks > 1:
         args.shard_plan = True
     return args
@@ -198,6 +216,44 @@ def load_hotwords(path: str, V: int):
     from zasr.hotword_context import parse_hotwords_file
     from zasr.model import hash_tokenize_phrases
     return hash_tokenize_phrases(parse_hotwords_file(path, 1.5), V)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy, float32 kept, everything else as
+    float64; an array that would take the dump past DUMP_LIMIT_BYTES is cut to a fixed seeded
+    sample of its rows (none of the stages' outputs come near it at the default sizes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > budget:
+            a = a.reshape(a.shape[0] if a.ndim else 1, -1)
+            keep = max(1, budget // max(1, a[0].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def ragged(rows):
+    """Per-chunk rows of differing length as one array, in chunk order."""
+    rows = [np.asarray(r) for r in rows]
+    rows = [r if r.dtype == np.float32 else r.astype(np.float64) for r in rows]
+    return np.concatenate(rows) if rows else np.zeros(0)
+
+
+def search_arrays(res, prefix=""):
+    """What a decode call returns for its chunks, as arrays: per chunk the token count and T',
+    and the chunks' token ids, emission frames, log-probs and token statistics end to end."""
+    out = {prefix + "tokens_per_chunk": [int(np.size(r.token_ids)) for r in res],
+           prefix + "encoder_frames": [int(r.T) for r in res]}
+    for name, attr in (("token_ids", "token_ids"), ("frames", "frames"),
+                       ("log_probs", "log_probs"), ("token_stats", "stats")):
+        if res and all(hasattr(r, attr) for r in res):
+            out[prefix + name] = ragged([getattr(r, attr) for r in res])
+    return out
 
 
 HOUR_GOLDEN = os.path.join(REPO, "tests", "golden", "bench_hour_oracle.json")
@@ -546,7 +602,7 @@ def bench_campp(args):
     feats = np.ascontiguousarray(np.stack(wins))
     W = feats.shape[0]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sample = feats[:64]
         mean, times = _campp_cpu(seed, sample, min(16, os.cpu_count() or 1), max(1, args.cpu_repeats))
         cpu = {"value": round(64 / W * args.audio_sec / mean, 3), "unit": "audio-sec/sec",
@@ -578,6 +634,8 @@ def bench_campp(args):
     if dist:
         from zasr.shard import max_over_ranks
         el = max_over_ranks(el, device=f"cuda:{local}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": d_out.cpu().numpy()})
     fl = W * campp_flops(cfg, 150)
     t_step = el / args.steps
     if rank == 0:
@@ -652,7 +710,7 @@ def bench_vad(args):
     nw = lens // 512
     NW = int(nw.sum())
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         n_s = 512 * 3000
         mean, times = _vad_cpu(seed, audio[:n_s], 1, max(1, args.cpu_repeats))
         cpu = {"value": round(n_s / SR / mean, 2), "unit": "audio-sec/sec", "cores": 1,
@@ -690,6 +748,11 @@ def bench_vad(args):
     if dist:
         from zasr.shard import max_over_ranks
         el = max_over_ranks(el, device=f"cuda:{local}")
+    if args.dump_outputs and rank == 0:  # the last step's probabilities and (file, start, end)
+        dump_outputs(args.dump_outputs,
+                     {"probs": d_probs[:NW].cpu().numpy(),
+                      "segments": np.array([(i, a, e) for i, sg in enumerate(segs) for a, e in sg],
+                                           np.float64).reshape(-1, 3)})
     # the recurrence alone, HIP events on the engine's ordering stream
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
@@ -823,7 +886,7 @@ def bench_pipe(args):
     # chunks / regions / ViBERT rows: FullPipe(shard=True)); else each rank its own hour
     audio = synth_speech(args.audio_sec, AUDIO_SEED + (0 if args.shard_plan else rank))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # before this process touches the GPU (spawned child); bounded sample: the first two
         # planner chunks and the speech regions they span
         import multiprocessing as mp
@@ -881,7 +944,7 @@ def bench_pipe(args):
         r = rs[-1]
         out.update(windows=len(r["windows"]), words=len(r["words"]), rows=r["vibert_rows"],
                    vibert_runs=r["vibert_runs"], tokens=r["tokens"],
-                   token_ids=[o["token_ids"] for o in rs])
+                   token_ids=[o["token_ids"] for o in rs], last=r)
 
     if args.warmup:
         steps(args.warmup)
@@ -897,6 +960,15 @@ def bench_pipe(args):
         from zasr.shard import max_over_ranks
         el = max_over_ranks(el, device=f"cuda:{local}")
     t_step = el / args.steps
+    if args.dump_outputs and rank == 0:  # the last timed pass of the hour
+        r = out["last"]
+        dump_outputs(args.dump_outputs,
+                     {"tokens_per_chunk": [len(t) for t in r["token_ids"]],
+                      "token_ids": ragged(r["token_ids"]),
+                      "word_times": np.array([(w["start"], w["end"]) for w in r["words"]],
+                                             np.float64).reshape(-1, 2),
+                      "embeddings": np.asarray(r["embeddings"], np.float32),
+                      "windows": r["windows"]})
     # stage times alone (one pass each, serialised): where the step goes
     stage_ms = {}
     main_st = torch.cuda.current_stream().cuda_stream
@@ -1057,7 +1129,7 @@ def bench_rover(args):
         from zasr.hotword_context import parse_hotwords_file
         phrases = [p for p, _ in parse_hotwords_file(hw_path, 1.5)]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # before this process touches the GPU (spawned child); bounded sample: the first chunk
         import multiprocessing as mp
         threads = min(16, os.cpu_count() or 1)
@@ -1101,7 +1173,8 @@ def bench_rover(args):
                               args.rover_passes_per_call, mine=mine,
                               gather=not (args.proxy_ranks > 1 and world == 1),
                               tokens_out=toks if keep else None)[-1]
-        last.update(words=len(r[0]), disagree_blocks=sum(r[1]), tokens_a=r[2], tokens_b=r[3])
+        last.update(words=len(r[0]), disagree_blocks=sum(r[1]), tokens_a=r[2], tokens_b=r[3],
+                    merged=r[0])
 
     if args.warmup:
         steps(args.warmup)
@@ -1119,6 +1192,13 @@ def bench_rover(args):
     # both models' tokens of every timed pass against the oracle's decode of this hour
     # (tests/golden/bench_hour_oracle_rover.json, make_bench_hour_golden.py --set rover)
     ochecks = rover_golden_checks(args, beam, phrases, chunks, toks) if toks else None
+    if args.dump_outputs and rank == 0:  # the last timed pass: merged words, both models' tokens
+        arrs = {"word_times": np.array([(w["start"], w["end"]) for w in last["merged"]],
+                                       np.float64).reshape(-1, 2)}
+        for m, t in zip(("30m", "68m"), toks[-1] if toks else ()):
+            arrs[f"tokens_per_chunk_{m}"] = [len(x) for x in t]
+            arrs[f"token_ids_{m}"] = ragged(t)
+        dump_outputs(args.dump_outputs, arrs)
     # each model alone (decode only, HIP work + result copies) for the breakdown
     alone = {}
     sel = list(range(len(lens))) if mine is None else mine
@@ -1376,6 +1456,7 @@ def bench_dropin(args):
     omap = [(0, 0, len(concat))]  # no VAD cut: the identity offset map (:2181)
     info = {}
 
+    last = {}
     split = {"regions": 0.0, "decode_start": 0.0, "decode": 0.0, "after_decode": 0.0, "merge": 0.0}
 
     def phase():
@@ -1412,6 +1493,7 @@ def bench_dropin(args):
         merged, _ = merge_chunks_with_overlap(results)
         t3 = time.perf_counter()
         info.update(chunks=len(plan), words=len(merged))
+        last["merged"] = merged
         # phase split (ms per step, summed over the timed steps): the planner call, the plan's
         # background decode, the workers' word building after it, the merge
         jobs = [j for sig in ae._planned[-1:] for per in sig.jobs.values() for j in per.values()]
@@ -1437,6 +1519,10 @@ def bench_dropin(args):
     if dist:
         from zasr.shard import max_over_ranks
         el = max_over_ranks(el, device=f"cuda:{local}")
+    if args.dump_outputs and rank == 0:  # the last phase's merged words
+        dump_outputs(args.dump_outputs,
+                     {"word_times": np.array([(w["start"], w["end"]) for w in last["merged"]],
+                                             np.float64).reshape(-1, 2)})
     if rank == 0:
         line = {"metric": "audio-sec/sec (xRT) drop-in decode_chunk loop (reference two-worker "
                           "dispatch), Zipformer-68M",
@@ -1578,7 +1664,7 @@ def main():
     lens = [c.shape[0] for c in chunks]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.cpu_dry_run:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.cpu_dry_run:
         cpu = cpu_baseline(args, chunks, beam, hotwords)
 
     import torch
@@ -1642,7 +1728,7 @@ def main():
         steps(args.warmup)
     sync()
     batch_latency_ms = None
-    if rec is not None:  # one batch alone (nothing to overlap with): reported beside
+    if rec is not None and args.full:  # one batch alone (nothing to overlap with): reported beside
         t1 = time.perf_counter()
         step()
         sync()
@@ -1663,11 +1749,13 @@ def main():
         from zasr.shard import max_over_ranks
         el = max_over_ranks(el, device=dev)
         dist.barrier()
+    if args.dump_outputs and rank == 0:  # the last timed step's results, as its caller got them
+        dump_outputs(args.dump_outputs, search_arrays(res))
 
     # kernel-class timing: HIP events recorded by the library on its launch stream over
     # profiled steps (separate from the wall-clock region above)
     classes, shapes, nprof = {}, None, max(1, min(args.steps, 3))
-    if rec is not None:
+    if rec is not None and args.full:
         rec.profile(1)
         rec.profile_reset()
         for _ in range(nprof):
@@ -1769,7 +1857,7 @@ def main():
     # the headline decode's tokens against the oracle's decode of the same hour (rank 0's
     # hour is the golden's; the other ranks decode seed + rank)
     ocheck = None
-    if rec is not None and rank == 0 and not args.shard_plan:
+    if rec is not None and args.full and rank == 0 and not args.shard_plan:
         golden = hour_golden(args, beam, hotwords, chunks)
         if golden is not None:
             ocheck = oracle_agreement(golden[0], golden[1], [[r.token_ids.tolist() for r in res]],
@@ -1781,7 +1869,7 @@ def main():
     # engine's copy stream under the previous batch's work (zasr_decode_host_batches) -- the
     # reference's unit of work starts from the host waveform (core/asr_engine.py:2068)
     host_line = None
-    if rec is not None and not args.no_pipeline and not args.shard_plan and lens:
+    if rec is not None and args.full and not args.no_pipeline and not args.shard_plan and lens:
         h_wav = torch.from_numpy(np.concatenate(chunks)).pin_memory()
         n = len(lens)
 
@@ -1810,20 +1898,21 @@ def main():
                              "copy stream under the previous batch's work"}
         del h_wav
     parity = None
-    if (rec is not None and world == 1 and args.parity_precision != "none"
+    if (rec is not None and args.full and world == 1 and args.parity_precision != "none"
             and args.parity_precision != args.precision):
         parity = run_parity_child()
     # configs 3, 4 and 5 in the token-exact mode, each in its own child process, beside the
     # default config-2 line (bounded: a few steps each)
     subs = None
-    if (rec is not None and world == 1 and not args.no_sub_lines and beam == 1 and
+    if (rec is not None and args.full and world == 1 and not args.no_sub_lines and beam == 1 and
             args.model == "zipformer-68m" and args.audio_sec == 3600.0 and not args.shard_plan
             and args.parity_precision not in ("none",)):
         k_sub = str(max(1, min(args.steps, 5)))
         subs = {}
         try:
             subs["config3_f16x3"] = sub_line(run_sub_bench(
-                ["--method", "modified_beam_search", "--beam", "8", "--hotwords-file", "default",
+                ["--full", "--method", "modified_beam_search", "--beam", "8",
+                 "--hotwords-file", "default",
                  "--precision", args.parity_precision, "--parity-precision", "none",
                  "--no-cpu-baseline", "--no-sub-lines", "--steps", k_sub, "--warmup", "1"]))
         except Exception as e:  # reported, never fatal to the headline line

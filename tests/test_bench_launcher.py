@@ -40,6 +40,27 @@ def test_bench_single_rank_default():
     assert 20.0 <= line["config"]["chunk_sec_min_max"][1] <= 36.0
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float32 / float64 .npy files, the
+    same from run to run (seeded inputs); --steps sets the number of timed steps."""
+    import numpy as np
+    lines, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        lines.append(_run("--dump-outputs", str(d)))
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+    assert {"token_ids.npy", "tokens_per_chunk.npy", "encoder_frames.npy"} <= set(dumps[0])
+    assert set(dumps[0]) == set(dumps[1])
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        assert np.array_equal(a, dumps[1][name]), name
+    n = lines[0]["config"]["chunks_per_gpu"]
+    assert dumps[0]["tokens_per_chunk.npy"].shape == (n,)
+    assert dumps[0]["token_ids.npy"].size == dumps[0]["tokens_per_chunk.npy"].sum() \
+        == lines[0]["config"]["tokens_emitted_per_gpu"]
+
+
 def test_bench_shard_plan_two_ranks_strong_scaling():
     """--shard-plan: both ranks plan the same audio, decode their LPT shares, gather every
     chunk's result in chunk order (gloo object gather here) inside the timed region; the line
