@@ -353,6 +353,16 @@ int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const 
 int zasr_selftest_ffn_bf16(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
                            const float* W2, const float* b2, const float* byp_orig,
                            const float* byp_scale, float* X, int32_t form);
+/* The attention kernels' block map alone (host only, no device call; no reference counterpart:
+   test infrastructure).  lens[nseq] frames per sequence, units_per_seq heads or z-chunks;
+   out[b] for block id b = sequence << 12 | unit << 8 | query tile (128 frames), or 0xffffffff
+   for an id past its range's end; block id b belongs to range b % 8, the units of range x
+   being contiguous in (sequence, unit) order and the 8 ranges near-equal in block-steps.
+   order 0: a range's slots run sequence -> tile -> unit (the decode's), 1: sequence -> unit ->
+   tile.  *grid = the launch's block count = 8 * the longest range's blocks; ZASR_ERR_INVALID
+   if it exceeds cap. */
+int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
+                                 int32_t order, uint32_t* out, int64_t cap, int32_t* grid);
 
 /* profiling: per-kernel-class HIP-event timing on the handle's stream.  on = 0 off,
    1 kernel classes, 2 kernel classes with the encoder GEMMs split by shape

@@ -12,10 +12,12 @@
 //   B = t1 transposed in bf16, [hid][R32] (sequence b in columns [o32_b, o32_b + L32_b), zero
 //       padded), i.e. the [N][K] "weight" layout the GEMM streams with 16-byte loads,
 // and the `* y` factor in its epilogue.  The kernels here produce A0 and t1^T.
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
+#include <vector>
 
 #include "common.h"
 #include "gemm.h"
@@ -140,13 +142,18 @@ __global__ __launch_bounds__(256) void attn_flash_kernel(AttnFlashArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 sVt[NP][2][12 * kKLd];
   // mode 3: V^T = t1t rows [fz NF 32, +NF 32) x 32 keys, keys permuted like sVt's
   __shared__ __attribute__((aligned(16))) __bf16 sVn[NP][2][MODE == 3 ? NF * 32 * kKLd : 8];
-  const int b = blockIdx.y;
-  const int h = W0 ? 0 : blockIdx.z;
-  const int fz = MODE == 3 ? blockIdx.z : 0;
+  // this block's (sequence, head or z-chunk, query tile) from the host-built map (kernels.h
+  // build_attn_block_map): ids of one XCD serve one contiguous run of sequences; the ids past
+  // a range's end hold the sentinel
+  const unsigned ent = a.map[blockIdx.x];
+  if (ent == kAttnMapNone) return;
+  const int b = ent >> 12;
+  const int unit = (ent >> 8) & 15;
+  const int h = W0 ? 0 : unit;
+  const int fz = MODE == 3 ? unit : 0;
   const int r0 = a.row_off[b];
   const int L = a.row_off[b + 1] - r0;
-  const int i0b = blockIdx.x * 128;
-  if (i0b >= L) return;
+  const int i0b = (ent & 255) * 128;
   const int H = a.H;
   const long ldq = 68L * H;
   const long ldv = 12L * H;
@@ -724,8 +731,7 @@ static void launch_flash_one(const AttnFlashArgs& a, dim3 grid, size_t lds, hipS
 }
 
 template <int NP, int FMT = 0>
-void launch_flash_np(const AttnFlashArgs& a, int mode, size_t lds, hipStream_t st) {
-  const dim3 grid(cdiv(a.max_len, 128), a.nseq, mode == 0 ? 1 : a.H);
+void launch_flash_np(const AttnFlashArgs& a, int mode, dim3 grid, size_t lds, hipStream_t st) {
   if (mode == 0)
     launch_flash_one<0, NP, FMT, 1>(a, grid, lds, st);
   else if (mode == 1)
@@ -736,41 +742,100 @@ void launch_flash_np(const AttnFlashArgs& a, int mode, size_t lds, hipStream_t s
 
 void launch_attn_flash(const AttnFlashArgs& a, int mode, hipStream_t st) {
   if (a.nseq <= 0 || a.max_len <= 0) return;
+  ZASR_REQUIRE(a.map && a.map_len > 0 && a.map_len % kAttnXcds == 0,
+               "attention: no block map (build_attn_block_map)");
+  ZASR_REQUIRE(a.max_len <= 128 * kAttnMapMaxTiles && a.nseq <= kAttnMapMaxSeq,
+               "attention: sequence count or length over the block map's fields");
+  // 1-D grid, one block per map entry
+  const dim3 grid(a.map_len);
   if (mode == 3) {
     ZASR_REQUIRE((a.pieces == 1 || a.pieces == kPiecesF16) && a.t1t && a.o8 && a.y && a.z &&
                      a.hid > 0 && a.hid % 4 == 0 && a.ldt % 8 == 0 && a.ldy % 4 == 0,
                  "attention mode 3: the bf16 or f16x3 mode, hid % 4 == 0");
     const size_t lds = (size_t)(a.max_len + kPosPad) * sizeof(float4);
-    // 5 fragments for hid = 144 (one chunk) and 288 (two), 6 for 192 (one) and 384 (two)
-    const int nft = cdiv(a.hid, 32);
-    if (a.pieces == kPiecesF16) {  // f16x3: two accumulators and two V^T images per fragment
+    // the map's units are the attn_nonlin_chunks(hid, pieces) z-chunks of attn_nonlin_frags
+    // fragments each
+    if (a.pieces == kPiecesF16) {
       // 3 value fragments per block (2 measured 4.87 vs 4.08 ms per hour)
-      const dim3 grid(cdiv(a.max_len, 128), a.nseq, cdiv(nft, 3));
       launch_flash_one<3, 2, 1, 3>(a, grid, lds, st);
       return;
     }
     // (one pass, online: 5-6 fragments at one wave per SIMD beat 4 fragments at two, 1.63 vs
     // 2.08 ms per hour; the two-pass form took 2.02)
-    const int nf = (nft % 5 == 0 || nft == 9) ? 5 : 6;
-    const dim3 grid(cdiv(a.max_len, 128), a.nseq, cdiv(nft, nf));
-    if (nf == 5)
+    if (attn_nonlin_frags(a.hid, a.pieces) == 5)
       launch_flash_one<3, 1, 0, 5>(a, grid, lds, st);
     else
       launch_flash_one<3, 1, 0, 6>(a, grid, lds, st);
     return;
   }
   ZASR_REQUIRE(a.H % 2 == 0, "attention: the bf16 kernels need an even head count (16-byte q/k rows)");
+  ZASR_REQUIRE(a.H <= kAttnMapMaxUnits, "attention: head count over the block map's field");
   const size_t lds = (size_t)(a.max_len + kPosPad) * sizeof(float4);
   if (a.pieces == 1)
-    launch_flash_np<1>(a, mode, lds, st);
+    launch_flash_np<1>(a, mode, grid, lds, st);
   else if (a.pieces == 2)
-    launch_flash_np<2>(a, mode, lds, st);
+    launch_flash_np<2>(a, mode, grid, lds, st);
   else if (a.pieces == 3)
-    launch_flash_np<3>(a, mode, lds, st);
+    launch_flash_np<3>(a, mode, grid, lds, st);
   else if (a.pieces == kPiecesF16)
-    launch_flash_np<2, 1>(a, mode, lds, st);
+    launch_flash_np<2, 1>(a, mode, grid, lds, st);
   else
     throw std::runtime_error("attention: pieces must be 1, 2, 3 or kPiecesF16");
+}
+
+// The block map of the flash kernels (kernels.h): host only.
+int build_attn_block_map(const int* lens, int nseq, int units, int order, std::vector<unsigned>& map) {
+  ZASR_REQUIRE(nseq >= 0 && nseq <= kAttnMapMaxSeq && units >= 1 && units <= kAttnMapMaxUnits &&
+                   (order == 0 || order == 1),
+               "attention block map: sequences, units per sequence or slot order out of range");
+  auto tiles = [](int L) { return (L + 127) / 128; };
+  auto weight = [&](int L) { return (long)tiles(L) * ((L + 31) / 32); };
+  long total = 0;
+  for (int b = 0; b < nseq; ++b) {
+    ZASR_REQUIRE(lens[b] >= 0 && tiles(lens[b]) <= kAttnMapMaxTiles,
+                 "attention block map: sequence length out of range");
+    total += weight(lens[b]) * units;
+  }
+  map.clear();
+  if (total == 0) return 0;
+  // the unit whose weight interval has its midpoint in [x total / 8, (x + 1) total / 8) goes to
+  // range x: contiguous, and no range is heavier than total / 8 + the largest unit weight.
+  // Per range, the runs (sequence, first unit, units) it holds
+  struct Run {
+    int seq, u0, n;
+  };
+  std::vector<Run> runs[kAttnXcds];
+  long before = 0;  // weight of the units listed so far
+  for (int b = 0; b < nseq; ++b) {
+    const long w = weight(lens[b]);
+    if (w == 0) continue;
+    for (int u = 0; u < units; ++u, before += w) {
+      const int x = (int)((2 * before + w) * kAttnXcds / (2 * total));
+      if (!runs[x].empty() && runs[x].back().seq == b)
+        ++runs[x].back().n;
+      else
+        runs[x].push_back(Run{b, u, 1});
+    }
+  }
+  long slots = 0;
+  for (const auto& rs : runs) {
+    long n = 0;
+    for (const Run& r : rs) n += (long)r.n * tiles(lens[r.seq]);
+    slots = std::max(slots, n);
+  }
+  ZASR_REQUIRE(slots * kAttnXcds <= INT32_MAX, "attention block map: too many blocks");
+  map.assign((size_t)slots * kAttnXcds, kAttnMapNone);
+  for (int x = 0; x < kAttnXcds; ++x) {
+    size_t slot = 0;
+    for (const Run& r : runs[x]) {
+      const int nt = tiles(lens[r.seq]);
+      for (int e = 0; e < nt * r.n; ++e) {
+        const int t = order == 0 ? e / r.n : e % nt, u = r.u0 + (order == 0 ? e % r.n : e / nt);
+        map[kAttnXcds * slot++ + x] = attn_map_pack(r.seq, u, t);
+      }
+    }
+  }
+  return (int)map.size();
 }
 
 // =====================================================================================

@@ -1082,7 +1082,8 @@ struct MetaPack {
 void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, const int* d_off,
                            const int* d_map,
                            const std::vector<int>& lens, const long* d_aoff,
-                           const void* d_slices_nl, int maxL, const int* d_o8, int R8, bool orig_ready, bool last_layer) {
+                           const void* d_slices_nl, int maxL, const int* d_o8, int R8,
+                           const AttnBlockMaps& bm, bool orig_ready, bool last_layer) {
   const int d = S.d, h = S.h, B = (int)lens.size();
   const int hid = 3 * d / 4;
   float* O = ws<float>("ly_orig", (size_t)R * d);
@@ -1116,8 +1117,11 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
     fa = AttnFlashArgs{qkp, h, Ly.pos_tab, model_.pmax, d_off, d_aoff, B, maxL, A,
                        nullptr, nullptr, stats, stats, np};
     if (np != kPiecesF16) {  // f16x3: consumed in the fused NonlinAttention kernel
+      AttnFlashArgs a = fa;
+      a.map = bm.head0;
+      a.map_len = bm.n_head0;
       prof_begin("attn_softmax");
-      launch_attn_flash(fa, 0, st_);
+      launch_attn_flash(a, 0, st_);
       prof_end();
     }
   } else {
@@ -1175,6 +1179,8 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
       AttnFlashArgs a = fa;
       a.v = vv;
       a.out = oa;
+      a.map = bm.heads;
+      a.map_len = bm.n_heads;
       prof_begin("attn_apply");
       launch_attn_flash(a, k == 0 ? 1 : 2, st_);
       prof_end();
@@ -1188,6 +1194,8 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
       AttnFlashArgs a = fa;
       a.v = vv;
       a.out = oa;
+      a.map = bm.heads;
+      a.map_len = bm.n_heads;
       prof_begin("attn_apply");
       launch_attn_flash(a, k == 0 ? 1 : 2, st_);
       prof_end();
@@ -1257,6 +1265,8 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
     a.y = h3 + 2 * hid;
     a.ldy = 3 * hid;
     a.z = z;
+    a.map = bm.head0;
+    a.map_len = bm.n_head0;
     prof_begin("attn_nonlin");
     launch_attn_flash(a, 3, st_);
     prof_end();
@@ -1281,6 +1291,8 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
       a.y = h3 + 2 * hid;
       a.ldy = 3 * hid;
       a.z = z;
+      a.map = bm.head0;
+      a.map_len = bm.n_head0;
       prof_begin("attn_nonlin");
       launch_attn_flash(a, 3, st_);
       prof_end();
@@ -1425,12 +1437,28 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
          o_L = mp.add(mL.off.data(), (B + 1) * 4), o_out = mp.add(mout.off.data(), (B + 1) * 4);
   size_t o_c2s = mp.add(sl_c2.data(), B * sizeof(GemmSlice)),
          o_c3s = mp.add(sl_c3.data(), B * sizeof(GemmSlice));
-  std::vector<size_t> o_st(ns), o_ao(ns), o_sn(ns), o_o8(ns);
+  std::vector<size_t> o_st(ns), o_ao(ns), o_sn(ns), o_o8(ns), o_bmh(ns), o_bm0(ns);
+  // the flash kernels' block maps (kernels.h build_attn_block_map), per stack: every head's
+  // (modes 1 / 2), and head 0's by z-chunk of the fused NonlinAttention (mode 3: the bf16 and
+  // f16x3 modes) or alone (mode 0: bf16x3 / bf16x6)
+  std::vector<int> n_bmh(ns, 0), n_bm0(ns, 0);
+  std::vector<unsigned> bmap;
   for (int i = 0; i < ns; ++i) {
     o_st[i] = mp.add(mst[i].off.data(), (B + 1) * 4);
     o_o8[i] = mp.add(o8[i].data(), (B + 1) * 4);
     o_ao[i] = mp.add(aoff[i].data(), B * sizeof(long));
     o_sn[i] = mp.add(sl_nl[i].data(), sl_nl[i].size() * sizeof(GemmSlice));
+    if (flash) {
+      const DStack& s = model_.stacks[i];
+      const int np = split_pieces();
+      const bool fused_nl = bf16 || np == kPiecesF16;
+      n_bmh[i] = build_attn_block_map(mst[i].len.data(), B, s.h, 0, bmap);
+      o_bmh[i] = mp.add(bmap.data(), bmap.size() * sizeof(unsigned));
+      n_bm0[i] = build_attn_block_map(mst[i].len.data(), B,
+                                      fused_nl ? attn_nonlin_chunks(3 * s.d / 4, bf16 ? 1 : np) : 1,
+                                      0, bmap);
+      o_bm0[i] = mp.add(bmap.data(), bmap.size() * sizeof(unsigned));
+    }
   }
   char* d_meta = ws<char>("enc_meta", mp.bytes.size());
   upload(d_meta, mp.bytes.data(), mp.bytes.size());
@@ -1580,7 +1608,10 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
     for (size_t li = 0; li < s.layers.size(); ++li)
       layer_forward(s, s.layers[li], X, mst[i].total, I(o_st[i]), st_map[i], mst[i].len,
                     reinterpret_cast<const long*>(d_meta + o_ao[i]), d_meta + o_sn[i],
-                    mst[i].maxlen, I(o_o8[i]), R8[i], li > 0, li + 1 == s.layers.size());
+                    mst[i].maxlen, I(o_o8[i]), R8[i],
+                    AttnBlockMaps{reinterpret_cast<const unsigned*>(d_meta + o_bmh[i]), n_bmh[i],
+                                  reinterpret_cast<const unsigned*>(d_meta + o_bm0[i]), n_bm0[i]},
+                    li > 0, li + 1 == s.layers.size());
     // seam: upsample + bypass combine, written as stack i+1's input and into the full-dim
     // output's channel range [d_later_max, d) (the latest stack that has those channels)
     int later_max = 0;

@@ -225,7 +225,8 @@ class Engine {
   ResPin res_pin_[kMaxJobs];
   void layer_forward(const DStack& stk, const DLayer& ly, float* X, int R, const int* d_off,
                      const int* d_map, const std::vector<int>& lens, const long* d_aoff,
-                     const void* d_slices_nl, int maxL, const int* d_o8, int R8, bool orig_ready = false,
+                     const void* d_slices_nl, int maxL, const int* d_o8, int R8,
+                     const AttnBlockMaps& bm, bool orig_ready = false,
                      bool last_layer = true);
   // byp_orig / byp_scale (split modes, EPI_RESADD): bypass_mid in the epilogue
   void linear(const DLin& l, const float* A, int lda, int M, float* C, int ldc, int epi,

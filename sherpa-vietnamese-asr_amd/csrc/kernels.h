@@ -5,6 +5,7 @@
 // need a row's sequence find it with a binary search over `off`.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -273,8 +274,49 @@ struct AttnFlashArgs {
   const void* y = nullptr;
   int ldy = 0;
   void* z = nullptr;
+  // block id -> (sequence, head or z-chunk, query tile) of this launch (build_attn_block_map:
+  // units = H for modes 1 / 2, 1 for mode 0, attn_nonlin_chunks for mode 3); the grid is 1-D,
+  // map_len blocks
+  const unsigned* map = nullptr;
+  int map_len = 0;
 };
 void launch_attn_flash(const AttnFlashArgs& a, int mode, hipStream_t st);
+// mode 3: value fragments (32 rows of t1^T) per block and the z-chunks of hid they make.  bf16:
+// 5 fragments for hid = 144 (one chunk) and 288 (two), 6 for 192 (one) and 384 (two); f16x3
+// (two accumulators and two V^T images per fragment): 3 per block
+inline int attn_nonlin_frags(int hid, int pieces) {
+  const int nft = (hid + 31) / 32;
+  if (pieces != 1) return 3;
+  return (nft % 5 == 0 || nft == 9) ? 5 : 6;
+}
+inline int attn_nonlin_chunks(int hid, int pieces) {
+  const int nf = attn_nonlin_frags(hid, pieces);
+  return ((hid + 31) / 32 + nf - 1) / nf;
+}
+// The flash kernels' block map (host only).  A unit is one (sequence, head or z-chunk) and
+// weighs cdiv(L, 128) * cdiv(L, 32) block-steps; the units, sequence-major, are cut into
+// kAttnXcds contiguous ranges of near-equal weight, and block id b serves slot b / kAttnXcds of
+// range b % kAttnXcds -- the XCD that the dispatcher deals block b to -- so the query tiles
+// and heads that read one sequence's K / V rows share one L2.  Entry b:
+// attn_map_pack(sequence, unit, tile), or kAttnMapNone past the range's end; only tiles with
+// tile * 128 < L get an entry (a sequence with L = 0 none).  order 0: the slots of a range run
+// sequence -> query tile -> unit (the engine's); 1: sequence -> unit -> query tile.  Returns
+// the grid size = kAttnXcds * (blocks of the longest range) = map.size().
+constexpr int kAttnXcds = 8;
+constexpr unsigned kAttnMapNone = 0xffffffffu;
+constexpr int kAttnMapMaxSeq = 1 << 20, kAttnMapMaxUnits = 16, kAttnMapMaxTiles = 256;
+inline unsigned attn_map_pack(int seq, int unit, int tile) {
+  return (unsigned)seq << 12 | (unsigned)unit << 8 | (unsigned)tile;
+}
+// one stack's device maps: every head's (modes 1 / 2), and head 0's (mode 3 by z-chunk, mode 0)
+struct AttnBlockMaps {
+  const unsigned* heads;
+  int n_heads;
+  const unsigned* head0;
+  int n_head0;
+};
+int build_attn_block_map(const int* lens, int nseq, int units_per_seq, int order,
+                         std::vector<unsigned>& map);
 // t1t[c][o8_b + j] = bf16(tanh(h3[r][c]) * h3[r][hid + c]) for packed row r = off_b + j;
 // columns [o8_b + L_b, o8_b + L8_b) zero; t1t row stride R8 = sum_b L8_b
 // pieces > 1 (an f32 h3, the split modes): piece t of every value at t1t + t * hid * R8

@@ -694,6 +694,18 @@ int zasr_selftest_ffn_bf16(int32_t R, int32_t D, int32_t F, const float* W1, con
   });
 }
 
+int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
+                                 int32_t order, uint32_t* out, int64_t cap, int32_t* grid) {
+  if (!lens || !grid || (cap > 0 && !out) || cap < 0) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::vector<unsigned> map;
+    *grid = zasr::build_attn_block_map(lens, nseq, units_per_seq, order, map);
+    if ((int64_t)map.size() > cap) return fail(ZASR_ERR_INVALID, "block map buffer too small");
+    std::copy(map.begin(), map.end(), out);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_silence_flags(const float* d_wav, int64_t n, int32_t frame_len, float threshold,
                        uint8_t* d_flags, void* stream) {
   if (n < 0 || (n > 0 && (!d_wav || !d_flags))) return fail(ZASR_ERR_INVALID, "null argument");

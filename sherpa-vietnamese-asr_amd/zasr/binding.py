@@ -36,6 +36,7 @@ EXPORTS = (
     "zasr_stream_result_json", "zasr_set_tokens", "zasr_model_routes",
     "zasr_fbank_set_mel_banks", "zasr_selftest_launch", "zasr_decode_host_batches",
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
+    "zasr_selftest_attn_block_map",
 )
 
 
@@ -219,6 +220,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_ffn_h3.restype = C.c_int
     lib.zasr_selftest_ffn_bf16.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, I32]
     lib.zasr_selftest_ffn_bf16.restype = C.c_int
+    lib.zasr_selftest_attn_block_map.argtypes = [C.POINTER(I32), I32, I32, I32,
+                                                 C.POINTER(C.c_uint32), I64, C.POINTER(I32)]
+    lib.zasr_selftest_attn_block_map.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -309,6 +313,26 @@ def selftest_ffn_bf16(W1, b1, W2, b2, X, byp_orig=None, byp_scale=None, form: in
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return X
+
+
+def selftest_attn_block_map(lens, units_per_seq: int, order: int = 0,
+                            lib_path: Optional[str] = None) -> np.ndarray:
+    """The attention kernels' block map alone, host only (zasr_selftest_attn_block_map):
+    returns the uint32 entry of every block id (sequence << 12 | unit << 8 | tile, 0xffffffff
+    past a range's end); its length is the launch's grid."""
+    lib = load_library(lib_path)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    # every (unit, tile) at most once per range, and a range may hold them all
+    cap = 8 * int(units_per_seq) * int(((lens.astype(np.int64) + 127) // 128).sum())
+    out = np.empty(max(cap, 1), dtype=np.uint32)
+    grid = C.c_int32(-1)
+    rc = lib.zasr_selftest_attn_block_map(lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens),
+                                          int(units_per_seq), int(order),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint32)), cap,
+                                          C.byref(grid))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out[:grid.value].copy()
 
 
 def silence_flags(d_wav_ptr: int, n: int, frame_len: int, threshold: float, d_flags_ptr: int,
