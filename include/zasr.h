@@ -353,6 +353,32 @@ int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const 
 int zasr_selftest_ffn_bf16(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
                            const float* W2, const float* b2, const float* byp_orig,
                            const float* byp_scale, float* X, int32_t form);
+/* The fused FFNs out of place (a layer's feed_forward1): the kernel reads X and writes
+   Xout = X + FFN(X) (then the bypass_mid blend), the same operations in the same order as the
+   in-place entries above (ffn_h3 with Y = X).  Xout holds its buffer's initial contents on
+   entry and the result on return; X returns what the input buffer holds afterwards. */
+int zasr_selftest_ffn_bf16_oop(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
+                               const float* W2, const float* b2, const float* byp_orig,
+                               const float* byp_scale, float* X, float* Xout, int32_t form);
+int zasr_selftest_ffn_h3_oop(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* byp_orig,
+                             const float* byp_scale, float* X, float* Xout);
+/* The fused stack seam (seam_kernel) and the three kernels it replaces, on the same host
+   operands (same conventions).  L[nseq] 50 Hz frames per sequence (>= 1), rows = sum L.  The
+   stack: width d, factor ds (1, 2, 4, 8), final X xd [sum ceil(L / ds)][d] (unused when
+   ds = 1), 50 Hz input orig [rows][d], bypass scale s [d].  y = orig + (xd[t / ds] - orig) s
+   (ds = 1: y = orig) is written to next [rows][dn] (truncated / zero-padded; dn = 0: none),
+   SimpleDownsample'd by ds_next with weights wn8 to xnext [sum ceil(L / ds_next)][dn]
+   (ds_next = 1: none), and, downsampled by 2 with weights wo2, to columns [c0, d) of out
+   [sum ceil(L / 2)][ldo] (c0 >= d: none).  next / xnext / out hold the buffers' initial
+   contents on entry and the fused kernel's on return; *_ref receive what stack_glue ->
+   downsample(next, ds_next) -> downsample(full-dim output, 2) leave in buffers with the same
+   initial contents (out_ref: only columns [c0, d) are meaningful). */
+int zasr_selftest_seam(int32_t nseq, const int32_t* L, int32_t d, int32_t ds, int32_t dn,
+                       int32_t ds_next, int32_t c0, int32_t ldo, const float* xd,
+                       const float* orig, const float* s, const float* wn8, const float* wo2,
+                       float* next, float* xnext, float* out, float* next_ref, float* xnext_ref,
+                       float* out_ref);
 /* The attention kernels' block map alone (host only, no device call; no reference counterpart:
    test infrastructure).  lens[nseq] frames per sequence, units_per_seq heads or z-chunks;
    out[b] for block id b = sequence << 12 | unit << 8 | query tile (128 frames), or 0xffffffff

@@ -849,6 +849,144 @@ void launch_stack_glue(const float* xd, const float* orig, const int* off_in, co
                      off_ds, map_in, rows, d / 4, shift, s, next, dn / 4, full, ldf / 4, c0 / 4);
 }
 
+// The whole seam in one pass (SeamArgs, kernels.h): stack_glue's y, then the two consumers
+// that would read `next` / the full-dim output straight back -- the next stack's
+// SimpleDownsample and the output downsample -- from y in registers.  A thread owns one float4
+// column group and a run of G consecutive 50 Hz frames of one sequence, G = the next stack's
+// factor (>= 2; the output downsample's 2 where the next stack has none): run r of the level
+// ceil(L / G) is row r of the next stack's X, and holds G / 2 output frames.  Every value is
+// computed by stack_glue_kernel's and downsample_kernel's own operations in their order (the
+// fmaf chain from u = 0 and acc = 0, frames past L - 1 replaced by frame L - 1).
+struct SeamArgs {
+  const float *xd, *orig, *s;
+  const int *off_in, *off_ds, *off_run, *map_run, *off_out;
+  int runs, d4, ds_shift;
+  float* next;
+  float* xnext;
+  int dn4;
+  float* out;
+  int ldo4, c04;
+  DsW wn;
+  float wo[2];
+};
+
+template <int G>
+__global__ void seam_kernel(SeamArgs a) {
+  const int d4 = a.d4, dn4 = a.dn4;
+  const int w4 = d4 > dn4 ? d4 : dn4;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.runs * w4) return;
+  const int r = e / w4, c4 = e - r * w4;
+  const int b = a.map_run[r];
+  const int tp = r - a.off_run[b];
+  const int base = a.off_in[b];
+  const int L = a.off_in[b + 1] - base;
+  const int t0 = tp * G;
+  float4 y[G];
+#pragma unroll
+  for (int u = 0; u < G; ++u) y[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c4 < d4) {
+    int t[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {  // all loads in flight
+      t[u] = t0 + u < L ? t0 + u : L - 1;
+      y[u] = reinterpret_cast<const float4*>(a.orig)[(base + t[u]) * d4 + c4];
+    }
+    if (a.ds_shift > 0) {
+      const int dsb = a.off_ds[b];
+      float4 up[G];
+#pragma unroll
+      for (int u = 0; u < G; ++u)
+        up[u] = reinterpret_cast<const float4*>(a.xd)[(dsb + (t[u] >> a.ds_shift)) * d4 + c4];
+      const float4 k = reinterpret_cast<const float4*>(a.s)[c4];
+#pragma unroll
+      for (int u = 0; u < G; ++u) {
+        const float4 o = y[u];
+        y[u].x = o.x + (up[u].x - o.x) * k.x;
+        y[u].y = o.y + (up[u].y - o.y) * k.y;
+        y[u].z = o.z + (up[u].z - o.z) * k.z;
+        y[u].w = o.w + (up[u].w - o.w) * k.w;
+      }
+    }
+  }
+  if (c4 < dn4) {
+    if (a.next != nullptr) {
+#pragma unroll
+      for (int u = 0; u < G; ++u)
+        if (t0 + u < L) reinterpret_cast<float4*>(a.next)[(base + t0 + u) * dn4 + c4] = y[u];
+    }
+    if (a.xnext != nullptr) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int u = 0; u < G; ++u) {
+        acc.x = fmaf(a.wn.w[u], y[u].x, acc.x);
+        acc.y = fmaf(a.wn.w[u], y[u].y, acc.y);
+        acc.z = fmaf(a.wn.w[u], y[u].z, acc.z);
+        acc.w = fmaf(a.wn.w[u], y[u].w, acc.w);
+      }
+      reinterpret_cast<float4*>(a.xnext)[r * dn4 + c4] = acc;
+    }
+  }
+  if (a.out != nullptr && c4 >= a.c04 && c4 < d4) {
+    const int ob = a.off_out[b] + tp * (G / 2);
+#pragma unroll
+    for (int k = 0; k < G / 2; ++k)
+      if (t0 + 2 * k < L) {  // output frame tp G / 2 + k < ceil(L / 2)
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          acc.x = fmaf(a.wo[u], y[2 * k + u].x, acc.x);
+          acc.y = fmaf(a.wo[u], y[2 * k + u].y, acc.y);
+          acc.z = fmaf(a.wo[u], y[2 * k + u].z, acc.z);
+          acc.w = fmaf(a.wo[u], y[2 * k + u].w, acc.w);
+        }
+        reinterpret_cast<float4*>(a.out)[(ob + k) * a.ldo4 + c4] = acc;
+      }
+  }
+}
+
+void launch_seam(const SeamDesc& s, hipStream_t st) {
+  const int G = s.ds_next >= 2 ? s.ds_next : 2;
+  const int w = s.d > s.dn ? s.d : s.dn;
+  const long n = (long)s.runs * (w / 4);
+  if (n <= 0) return;
+  ZASR_REQUIRE(s.d % 4 == 0 && s.dn % 4 == 0 && s.ldo % 4 == 0 && s.c0 % 4 == 0 &&
+                   (long)s.rows * (w / 4) < (1L << 31),
+               "seam: widths must be multiples of 4");
+  ZASR_REQUIRE(G == 2 || G == 4 || G == 8, "seam: the next stack's factor must be 1, 2, 4 or 8");
+  ZASR_REQUIRE(s.xnext == nullptr || (s.ds_next >= 2 && s.dn > 0),
+               "seam: a downsampled next stack needs its factor and width");
+  ZASR_REQUIRE(s.out == nullptr || s.off_out != nullptr, "seam: output columns need their offsets");
+  int shift = 0;
+  while ((1 << shift) < s.ds) ++shift;
+  ZASR_REQUIRE((1 << shift) == s.ds, "seam: downsampling factor must be a power of 2");
+  SeamArgs a{};
+  a.xd = s.xd;
+  a.orig = s.orig;
+  a.s = s.s;
+  a.off_in = s.off_in;
+  a.off_ds = s.off_ds;
+  a.off_run = s.off_run;
+  a.map_run = s.map_run;
+  a.off_out = s.off_out;
+  a.runs = s.runs;
+  a.d4 = s.d / 4;
+  a.ds_shift = shift;
+  a.next = s.next;
+  a.xnext = s.xnext;
+  a.dn4 = s.dn / 4;
+  a.out = s.c0 < s.d ? s.out : nullptr;
+  a.ldo4 = s.ldo / 4;
+  a.c04 = s.c0 / 4;
+  for (int u = 0; u < 8; ++u) a.wn.w[u] = s.xnext != nullptr && u < G ? s.wn_host8[u] : 0.f;
+  for (int u = 0; u < 2; ++u) a.wo[u] = a.out != nullptr ? s.wo_host2[u] : 0.f;
+#define ZASR_SEAM(GV) ZASR_LAUNCH((seam_kernel<GV>), dim3(cdivl(n, 256)), dim3(256), 0, st, a)
+  if (G == 2) ZASR_SEAM(2);
+  else if (G == 4) ZASR_SEAM(4);
+  else ZASR_SEAM(8);
+#undef ZASR_SEAM
+}
+
 __global__ void upsample_combine_kernel(const float* __restrict__ xd,
                                         const float* __restrict__ orig,
                                         const int* __restrict__ off_in,

@@ -1079,16 +1079,30 @@ struct MetaPack {
 };
 }  // namespace
 
-void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, const int* d_off,
-                           const int* d_map,
-                           const std::vector<int>& lens, const long* d_aoff,
-                           const void* d_slices_nl, int maxL, const int* d_o8, int R8,
-                           const AttnBlockMaps& bm, bool orig_ready, bool last_layer) {
+// feed_forward1 on a fused kernel (the ff lambda's routes below): it can run out of place
+bool Engine::ff1_fused(const DStack& S, const DLayer& Ly) const {
+  const DLin& fi = Ly.ff_in[0];
+  if (fi.wh) return ffn_fused_supported(S.d) && (S.d < 256 || fi.wp);
+  return fi.wp && split_pieces() == kPiecesF16 && ffn_h3_oop_ok(S.d);
+}
+
+float* Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, float* Xalt, int R,
+                             const int* d_off, const int* d_map,
+                             const std::vector<int>& lens, const long* d_aoff,
+                             const void* d_slices_nl, int maxL, const int* d_o8, int R8,
+                             const AttnBlockMaps& bm, bool orig_ready, bool copy_for_next) {
   const int d = S.d, h = S.h, B = (int)lens.size();
   const int hid = 3 * d / 4;
-  float* O = ws<float>("ly_orig", (size_t)R * d);
-  if (!orig_ready)  // else the previous layer's BiasNorm already wrote src here
-    ZASR_HIP_CHECK(hipMemcpyAsync(O, X, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, st_));
+  // O = the layer's input (src of bypass_mid and the final bypass).  A fused feed_forward1
+  // reads it from X and writes Xalt, where the rest of the layer runs in place: X itself stays
+  // as O.  The GEMM-pair routes update X in place, so they keep a copy.
+  const bool oop = ff1_fused(S, Ly);
+  float* O = X;
+  if (!oop) {
+    O = ws<float>("ly_orig", (size_t)R * d);
+    if (!orig_ready)  // else the previous layer's BiasNorm already wrote src here
+      ZASR_HIP_CHECK(hipMemcpyAsync(O, X, (size_t)R * d * sizeof(float), hipMemcpyDeviceToDevice, st_));
+  }
   // attention weights (shared by nonlin_attention, self_attn1, self_attn2)
   const bool bf16 = precision_ == 1 || precision_ == 2;
   const int np = split_pieces();
@@ -1138,7 +1152,7 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
   }
   // bf16 mode: feed_forward2's residual epilogue also applies bypass_mid (same formula as
   // launch_bypass, one pass over X fewer)
-  auto ff = [&](int k) {
+  auto ff = [&](int k, const float* src = nullptr) {  // src: out of place (fused routes only)
     const DLin& fi = Ly.ff_in[k];
     const float* bo = (bf16 && k == 1) ? O : nullptr;
     const float* bs = (bf16 && k == 1) ? Ly.bypass_mid : nullptr;
@@ -1147,10 +1161,12 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
       // (d >= 256: the fragment-packed weights of ffn_wide_kernel)
       prof_begin("ffn_fused");
       launch_ffn_fused(X, R, d, fi.N, d < 256 ? fi.wh : fi.wp, fi.b,
-                       d < 256 ? Ly.ff_out[k].wh : Ly.ff_out[k].wp, Ly.ff_out[k].b, st_, bo, bs);
+                       d < 256 ? Ly.ff_out[k].wh : Ly.ff_out[k].wp, Ly.ff_out[k].b, st_, bo, bs, src);
       prof_end();
       return;
     }
+    ZASR_REQUIRE(src == nullptr || (!fi.wh && fi.wp && np == kPiecesF16),
+                 "feed-forward: only the fused kernels run out of place");
     if (fi.wh) {  // bf16 mode: the hidden activation crosses HBM in bf16
       __bf16* H = ws<__bf16>("ly_hid_h", (size_t)R * fi.N);
       linear_h(fi, X, false, d, R, H, true, fi.N, EPI_SWOOSHL);
@@ -1160,7 +1176,7 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
       // feed_forward2 folds bypass_mid as the GEMM pair's residual epilogue does
       prof_begin("ffn_fused");
       launch_ffn_fused_h3(X, R, d, fi.N, fi.wp, fi.b, Ly.ff_out[k].wp, Ly.ff_out[k].b, st_,
-                          k == 1 ? O : nullptr, k == 1 ? Ly.bypass_mid : nullptr);
+                          k == 1 ? O : nullptr, k == 1 ? Ly.bypass_mid : nullptr, nullptr, src);
       prof_end();
     } else {
       // split modes: feed_forward2's epilogue applies bypass_mid too (fp32: launch_bypass)
@@ -1243,8 +1259,13 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
     }
     linear(Ly.cv_out[k], dc, d, R, X, d, EPI_RESADD);
   };
-  // 1. feed_forward1
-  ff(0);
+  // 1. feed_forward1 (fused: O -> Xalt, the layer's X from here on)
+  if (oop) {
+    X = Xalt;
+    ff(0, O);
+  } else {
+    ff(0);
+  }
   // 2. nonlin_attention (attention head 0 only)
   if (bf16) {
     // z = (A0 @ t1) * y with t1^T [hid][R8] bf16, z bf16; (s, x, y) = chunk(in_proj(src), 3)
@@ -1361,8 +1382,12 @@ void Engine::layer_forward(const DStack& S, const DLayer& Ly, float* X, int R, c
   // squares reduced across the block's waves, X read twice -- measured slower: ffn_fused
   // +1.26 ms, elementwise -0.78 ms per hour)
   prof_begin("elementwise");
-  launch_bias_norm(X, R, d, Ly.norm_b, Ly.norm_ls, O, Ly.bypass, st_, last_layer ? nullptr : O);
+  // (copy_for_next: the next layer's feed_forward1 is a GEMM pair and takes its copy of src
+  // from here; written over `orig` where that is the copy, which the same lane has read)
+  launch_bias_norm(X, R, d, Ly.norm_b, Ly.norm_ls, O, Ly.bypass, st_,
+                   copy_for_next ? ws<float>("ly_orig", (size_t)R * d) : nullptr);
   prof_end();
+  return X;
 }
 
 void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float* d_enc,
@@ -1585,51 +1610,94 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
   else
     ws<float>("ly_attn", split_pieces() == kPiecesF16 ? 1 : std::max<size_t>(attn_floats, 1));
   const int Dm = cfg.max_dim();
-  float* full = ws<float>("st_full", (size_t)mL.total * Dm);
-  // stack i's input (50 Hz, width d_i): stack 0 takes the embed output, every later one is
-  // written by the previous seam's stack_glue
-  float* orig = ws<float>("st_orig0", (size_t)mL.total * model_.stacks[0].d);
-  prof_begin("elementwise");
-  launch_copy_cols(e0, d0, 0, orig, model_.stacks[0].d, 0, std::min(d0, model_.stacks[0].d),
-                   mL.total, true, model_.stacks[0].d, st_);
-  prof_end();
+  // the 25 Hz full-dim output: each column range is written by the seam of the latest stack
+  // that has it
+  float* fo = ws<float>("enc_ds", (size_t)mout.total * Dm);
+  // stack i's input (50 Hz, width d_i): stack 0 takes the embed output (itself where the
+  // widths agree), every later one is written by the previous seam
+  float* orig = e0;
+  if (d0 != model_.stacks[0].d) {
+    orig = ws<float>("st_orig0", (size_t)mL.total * model_.stacks[0].d);
+    prof_begin("elementwise");
+    launch_copy_cols(e0, d0, 0, orig, model_.stacks[0].d, 0, std::min(d0, model_.stacks[0].d),
+                     mL.total, true, model_.stacks[0].d, st_);
+    prof_end();
+  }
+  // the running stack's second X buffer (layer_forward), sized for the largest stack
+  size_t xalt_n = 1;
+  for (int i = 0; i < ns; ++i) xalt_n = std::max(xalt_n, (size_t)mst[i].total * model_.stacks[i].d);
+  float* xalt = ws<float>("st_xalt", xalt_n);
+  // a downsampled stack's X (its own rate) is written by the seam ahead of it, which still
+  // reads the previous stack's: st_x0 / st_x1 in turn
+  float* Xds = nullptr;
+  if (model_.stacks[0].ds > 1) {  // no seam ahead of stack 0
+    const DStack& s = model_.stacks[0];
+    Xds = ws<float>("st_x0", (size_t)mst[0].total * s.d);
+    prof_begin("elementwise");
+    launch_downsample(orig, I(o_L), I(o_st[0]), st_map[0], mst[0].total, s.d, s.ds, s.ds_w, Xds, st_);
+    prof_end();
+  }
   for (int i = 0; i < ns; ++i) {
     const DStack& s = model_.stacks[i];
     const int d = s.d;
-    float* X;
-    if (s.ds == 1) {
-      X = orig;
-    } else {
-      X = ws<float>("st_x", (size_t)mst[i].total * d);
-      prof_begin("elementwise");
-      launch_downsample(orig, I(o_L), I(o_st[i]), st_map[i], mst[i].total, d, s.ds, s.ds_w, X, st_);
-      prof_end();
+    // the stack's X and a second buffer: a layer whose feed_forward1 is fused leaves its
+    // output in the other one, and the next layer swaps their roles
+    float* X = s.ds == 1 ? orig : Xds;
+    float* Xalt = xalt;
+    bool orig_ready = false;
+    for (size_t li = 0; li < s.layers.size(); ++li) {
+      const bool copy_for_next = li + 1 < s.layers.size() && !ff1_fused(s, s.layers[li + 1]);
+      float* Xo = layer_forward(s, s.layers[li], X, Xalt, mst[i].total, I(o_st[i]), st_map[i],
+                                mst[i].len, reinterpret_cast<const long*>(d_meta + o_ao[i]),
+                                d_meta + o_sn[i], mst[i].maxlen, I(o_o8[i]), R8[i],
+                                AttnBlockMaps{reinterpret_cast<const unsigned*>(d_meta + o_bmh[i]), n_bmh[i],
+                                              reinterpret_cast<const unsigned*>(d_meta + o_bm0[i]), n_bm0[i]},
+                                orig_ready, copy_for_next);
+      if (Xo != X) std::swap(X, Xalt);
+      orig_ready = copy_for_next;
     }
-    for (size_t li = 0; li < s.layers.size(); ++li)
-      layer_forward(s, s.layers[li], X, mst[i].total, I(o_st[i]), st_map[i], mst[i].len,
-                    reinterpret_cast<const long*>(d_meta + o_ao[i]), d_meta + o_sn[i],
-                    mst[i].maxlen, I(o_o8[i]), R8[i],
-                    AttnBlockMaps{reinterpret_cast<const unsigned*>(d_meta + o_bmh[i]), n_bmh[i],
-                                  reinterpret_cast<const unsigned*>(d_meta + o_bm0[i]), n_bm0[i]},
-                    li > 0, li + 1 == s.layers.size());
-    // seam: upsample + bypass combine, written as stack i+1's input and into the full-dim
-    // output's channel range [d_later_max, d) (the latest stack that has those channels)
+    // seam (seam_kernel): upsample + bypass combine, written as stack i+1's 50 Hz input, as
+    // its SimpleDownsample'd X, and, downsampled by 2, into the encoder output's channel range
+    // [d_later_max, d) (the latest stack that has those channels)
     int later_max = 0;
     for (int j = i + 1; j < ns; ++j) later_max = std::max(later_max, model_.stacks[j].d);
-    const int dn = i + 1 < ns ? model_.stacks[i + 1].d : 0;
-    float* next = i + 1 < ns ? ws<float>("st_orig" + std::to_string((i + 1) % 2), (size_t)mL.total * dn)
-                             : nullptr;
+    const bool more = i + 1 < ns;
+    const int dn = more ? model_.stacks[i + 1].d : 0;
+    const int dsn = more ? model_.stacks[i + 1].ds : 1;
+    SeamDesc sd;
+    sd.xd = X;
+    sd.orig = s.ds == 1 ? X : orig;  // ds == 1: y is the stack's final X, whichever buffer
+    sd.s = s.comb;
+    sd.off_in = I(o_L);
+    sd.off_ds = I(o_st[i]);
+    sd.off_run = dsn > 1 ? I(o_st[i + 1]) : I(o_out);
+    sd.map_run = dsn > 1 ? st_map[i + 1] : out_map;
+    sd.runs = dsn > 1 ? mst[i + 1].total : mout.total;
+    sd.rows = mL.total;
+    sd.d = d;
+    sd.ds = s.ds;
+    sd.next = more ? ws<float>("st_orig" + std::to_string((i + 1) % 2), (size_t)mL.total * dn)
+                   : nullptr;
+    sd.dn = dn;
+    sd.ds_next = dsn;
+    if (dsn > 1) {
+      sd.xnext = ws<float>("st_x" + std::to_string((i + 1) % 2), (size_t)mst[i + 1].total * dn);
+      sd.wn_host8 = model_.stacks[i + 1].ds_w;
+    }
+    if (d > later_max) {
+      sd.out = fo;
+      sd.off_out = I(o_out);
+      sd.wo_host2 = model_.out_ds_w;
+      sd.ldo = Dm;
+      sd.c0 = later_max;
+    }
     prof_begin("elementwise");
-    launch_stack_glue(X, orig, I(o_L), I(o_st[i]), L_map, mL.total, d, s.ds, s.comb, next, dn,
-                      d > later_max ? full : nullptr, Dm, later_max, st_);
+    launch_seam(sd, st_);
     prof_end();
-    orig = next;
+    orig = sd.next;
+    Xds = sd.xnext;
   }
-  // ---------------- output downsample + encoder_proj ----------------
-  float* fo = ws<float>("enc_ds", (size_t)mout.total * Dm);
-  prof_begin("elementwise");
-  launch_downsample(full, I(o_L), I(o_out), out_map, mout.total, Dm, 2, model_.out_ds_w, fo, st_);
-  prof_end();
+  // ---------------- encoder_proj ----------------
   linear(model_.enc_proj, fo, Dm, mout.total, d_enc, cfg.joiner_dim, EPI_NONE);
 }
 

@@ -223,11 +223,15 @@ class Engine {
     size_t cap = 0;
   };
   ResPin res_pin_[kMaxJobs];
-  void layer_forward(const DStack& stk, const DLayer& ly, float* X, int R, const int* d_off,
-                     const int* d_map, const std::vector<int>& lens, const long* d_aoff,
-                     const void* d_slices_nl, int maxL, const int* d_o8, int R8,
-                     const AttnBlockMaps& bm, bool orig_ready = false,
-                     bool last_layer = true);
+  // X: the layer's input; Xalt: a second buffer of its size.  Returns the one that holds the
+  // output: Xalt when feed_forward1 ran out of place (ff1_fused; X then stays as the input),
+  // else X.  orig_ready: the previous layer wrote this layer's copy of its input (ly_orig);
+  // copy_for_next: write the next layer's.
+  float* layer_forward(const DStack& stk, const DLayer& ly, float* X, float* Xalt, int R,
+                       const int* d_off, const int* d_map, const std::vector<int>& lens,
+                       const long* d_aoff, const void* d_slices_nl, int maxL, const int* d_o8,
+                       int R8, const AttnBlockMaps& bm, bool orig_ready, bool copy_for_next);
+  bool ff1_fused(const DStack& stk, const DLayer& ly) const;
   // byp_orig / byp_scale (split modes, EPI_RESADD): bypass_mid in the epilogue
   void linear(const DLin& l, const float* A, int lda, int M, float* C, int ldc, int epi,
               const char* cls = "enc_gemm", const float* byp_orig = nullptr,

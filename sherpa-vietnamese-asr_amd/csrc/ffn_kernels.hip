@@ -80,14 +80,19 @@ __device__ __forceinline__ void lds_signal(int* p, int lane) {
   if (lane == 0) __hip_atomic_fetch_add(p, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <int D>
+// OOP (all four kernels): out of place -- the token rows and the residual are read from Xsrc,
+// the result is written to X, Xsrc's rows stay as they were (X and Xsrc must not overlap).
+// !OOP: in place, Xsrc is not read and every instantiation compiles as it did without it.
+template <int D, bool OOP = false>
 __global__ __launch_bounds__(256, (D <= 192 ? 2 : 1)) void ffn_fused_kernel(float* __restrict__ X, int R, int F,
                                                            const __bf16* __restrict__ W1,
                                                            const float* __restrict__ b1,
                                                            const __bf16* __restrict__ W2,
                                                            const float* __restrict__ b2,
                                                            const float* __restrict__ byp_orig,
-                                                           const float* __restrict__ byp_scale) {
+                                                           const float* __restrict__ byp_scale,
+                                                           const float* __restrict__ Xsrc) {
+  const float* Xin = OOP ? Xsrc : X;
   constexpr int KS = D / 16;     // k-steps of the first product
   constexpr int OT = D / 32;     // output row tiles of the second
   constexpr int W1LD = D + 8;    // W1 chunk row stride (bf16): odd multiple of 16 B
@@ -162,7 +167,7 @@ __global__ __launch_bounds__(256, (D <= 192 ? 2 : 1)) void ffn_fused_kernel(floa
   // ---- this lane's token row as X^T fragments: element j of k-step s = X[tok][16 s + 8 h2 + j] ----
   bf16x8 xf[KS];
   {
-    const float* xr = X + (long)tokc * D + 8 * h2;
+    const float* xr = Xin + (long)tokc * D + 8 * h2;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const float4 a = *reinterpret_cast<const float4*>(xr + 16 * s);
@@ -213,13 +218,14 @@ __global__ __launch_bounds__(256, (D <= 192 ? 2 : 1)) void ffn_fused_kernel(floa
   // ---- X[tok][d] += O^T + b2: lane's token, channels t*32 + 8 g + 4 h2 + (0..3) ----
   if (tok >= R) return;
   float* xr = X + (long)tok * D;
+  const float* xi = OOP ? Xin + (long)tok * D : xr;
 #pragma unroll
   for (int t = 0; t < OT; ++t)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int ch = t * 32 + 8 * g + 4 * h2;
       const float4 bb = *reinterpret_cast<const float4*>(b2 + ch);
-      float4 v = *reinterpret_cast<const float4*>(xr + ch);
+      float4 v = *reinterpret_cast<const float4*>(xi + ch);
       v.x += o[t][4 * g + 0] + bb.x;
       v.y += o[t][4 * g + 1] + bb.y;
       v.z += o[t][4 * g + 2] + bb.z;
@@ -250,14 +256,16 @@ __global__ __launch_bounds__(256, (D <= 192 ? 2 : 1)) void ffn_fused_kernel(floa
 // phase ahead: the chunk's W2 fragments are issued before its phase A, the next chunk's W1
 // fragments right after this chunk's phase A.  Two barriers per chunk around the H write.
 // Epilogue as above: X += O^T + b2 (+ bypass_mid).
-template <int D, bool EB = true>
+template <int D, bool EB = true, bool OOP = false>
 __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X, int R, int F,
                                                           const __bf16* __restrict__ W1,
                                                           const float* __restrict__ b1,
                                                           const __bf16* __restrict__ W2,
                                                           const float* __restrict__ b2,
                                                           const float* __restrict__ byp_orig,
-                                                          const float* __restrict__ byp_scale) {
+                                                          const float* __restrict__ byp_scale,
+                                                          const float* __restrict__ Xsrc) {
+  const float* Xin = OOP ? Xsrc : X;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   constexpr int TT = 64, HC = 128, NW = 8;
   // bf16 row strides of 16 (8 k + 2) bytes: the 16x16x32 operand reads (row = lane & 15,
@@ -285,7 +293,7 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
     for (int i = 0; i < NE; ++i) {
       const int e = tid + 64 * NW * i, row = e / (D / 4), c4 = e - row * (D / 4);
       const long r = t0 + row < R ? t0 + row : R - 1;
-      v[i] = *reinterpret_cast<const float4*>(X + r * D + 4 * c4);
+      v[i] = *reinterpret_cast<const float4*>(Xin + r * D + 4 * c4);
     }
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
@@ -429,7 +437,7 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
 #pragma unroll
       for (int t = 0; t < OT; ++t) {
         const int ch = wid * OW + 16 * t + 4 * g4;
-        xv[du][t] = *reinterpret_cast<const float4*>(X + tok * D + ch);
+        xv[du][t] = *reinterpret_cast<const float4*>(Xin + tok * D + ch);
         if (byp_orig != nullptr) b0v[du][t] = *reinterpret_cast<const float4*>(byp_orig + tok * D + ch);
       }
     }
@@ -465,11 +473,12 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
     const long tok = t0 + 16 * u + r16;
     if (tok >= R) continue;
     float* xr = X + tok * D;
+    const float* xi = OOP ? Xin + tok * D : xr;
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
       const int ch = wid * OW + 16 * t + 4 * g4;
       const float4 bv = *reinterpret_cast<const float4*>(b2 + ch);
-      float4 v = *reinterpret_cast<const float4*>(xr + ch);
+      float4 v = *reinterpret_cast<const float4*>(xi + ch);
       v.x += o[t][u][0] + bv.x;
       v.y += o[t][u][1] + bv.y;
       v.z += o[t][u][2] + bv.z;
@@ -494,7 +503,7 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
 // (tools/ffnw_lab.hip, profiles/r06/ffn_rows/).  Not at d = 256 (0.82-0.87x: one block per
 // tile runs two blocks per CU whose X staging and epilogues overlap each other's chunks; the
 // rows form at two blocks per CU spills) nor d = 512 (0.95x, spills).
-template <int D, bool EB>
+template <int D, bool EB, bool OOP = false>
 __global__ __launch_bounds__(512, 2) void ffn_rows_kernel(float* __restrict__ X, int R, int F,
                                                           const __bf16* W1,
                                                           const float* __restrict__ b1,
@@ -502,7 +511,8 @@ __global__ __launch_bounds__(512, 2) void ffn_rows_kernel(float* __restrict__ X,
                                                           const float* __restrict__ b2,
                                                           const float* __restrict__ byp_orig,
                                                           const float* __restrict__ byp_scale,
-                                                          int rpb) {
+                                                          int rpb, const float* __restrict__ Xsrc) {
+  const float* Xin = OOP ? Xsrc : X;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   constexpr int TUM = 4, HC = 128, NW = 8;
   constexpr int XLD = D + 16, HLD = HC + 16;  // as ffn_wide_kernel
@@ -559,7 +569,7 @@ __global__ __launch_bounds__(512, 2) void ffn_rows_kernel(float* __restrict__ X,
       for (int i = 0; i < NE; ++i) {
         const int e = tix + 64 * NW * i, row = e / (D / 4), c4 = e - row * (D / 4);
         const long r = t0 + row < R ? t0 + row : R - 1;
-        v[i] = *reinterpret_cast<const float4*>(X + r * D + 4 * c4);
+        v[i] = *reinterpret_cast<const float4*>(Xin + r * D + 4 * c4);
       }
 #pragma unroll
       for (int i = 0; i < NE; ++i) {
@@ -661,7 +671,7 @@ __global__ __launch_bounds__(512, 2) void ffn_rows_kernel(float* __restrict__ X,
 #pragma unroll
         for (int t = 0; t < OT; ++t) {
           const int ch = wid * OW + 16 * t + 4 * g4e;
-          xv[du][t] = *reinterpret_cast<const float4*>(X + tok * D + ch);
+          xv[du][t] = *reinterpret_cast<const float4*>(Xin + tok * D + ch);
           if (byp_orig != nullptr) b0v[du][t] = *reinterpret_cast<const float4*>(byp_orig + tok * D + ch);
         }
       }
@@ -779,7 +789,7 @@ __device__ __forceinline__ void mfma16_h3(f32x4v& acc, const f16x8& wh, const f1
 // of their SIMD partners) run their low phase-B MFMAs while the partners are still in
 // SwooshL, instead of idling at a block barrier (per-wave stamps: profiles/r06/ffn_pp/).
 // Same products in the same order: bit-identical to the barrier form.
-template <int D, int TUM, int NB, int NW, bool SB = false, bool EB = false>
+template <int D, int TUM, int NB, int NW, bool SB = false, bool EB = false, bool OOP = false>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __restrict__ X, int R, int F,
                                                              const __bf16* __restrict__ W1,
                                                              const float* __restrict__ b1,
@@ -788,6 +798,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __r
                                                              const float* __restrict__ byp_orig,
                                                              const float* __restrict__ byp_scale,
                                                              int rpb, const float* __restrict__ Y) {
+  const float* Xin = OOP ? Y : X;  // the residual's source: out of place, the token rows' own
   constexpr int HC = 16 * NW, TTM = 16 * TUM;  // NW waves: 8 (one block per CU), 4 (two)
   constexpr int XLD = D + 16, HLD = HC + 16;  // 16 (8 k + 2)-byte rows, as ffn_wide_kernel
   constexpr int KS = D / 32;
@@ -1041,7 +1052,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __r
 #pragma unroll
         for (int t = 0; t < OT; ++t) {
           const int ch = wid * OW + 16 * t + 4 * g4;
-          xv[du][t] = *reinterpret_cast<const float4*>(X + tok * D + ch);
+          xv[du][t] = *reinterpret_cast<const float4*>(Xin + tok * D + ch);
           if (byp_orig != nullptr) b0v[du][t] = *reinterpret_cast<const float4*>(byp_orig + tok * D + ch);
         }
       }
@@ -1077,11 +1088,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __r
     const long tok = t0 + 16 * u + r16;
     if (tok >= r1) continue;
     float* xr = X + tok * D;
+    const float* xi = OOP ? Xin + tok * D : xr;
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
       const int ch = wid * OW + 16 * t + 4 * g4;
       const float4 bv = *reinterpret_cast<const float4*>(b2 + ch);
-      float4 v = *reinterpret_cast<const float4*>(xr + ch);
+      float4 v = *reinterpret_cast<const float4*>(xi + ch);
       v.x += o[t][u][0] * kF16LoInv + bv.x;
       v.y += o[t][u][1] * kF16LoInv + bv.y;
       v.z += o[t][u][2] * kF16LoInv + bv.z;
@@ -1136,6 +1148,12 @@ bool ffn_h3_supported(int D, int F) {
          (D == 192 && F % 64 == 0 && F >= 64);
 }
 
+// Out of place the epilogue holds a load and a store address per row: d = 128 starts to spill
+// (0 -> 12 bytes of scratch per lane) and d = 512 spills more (64 -> 72); 192 / 384 compile to
+// the in-place kernel's registers and scratch, 256 to 2 VGPRs more (254, no scratch).  The
+// encoder keeps its copy of the layer input at 128 and 512.
+bool ffn_h3_oop_ok(int D) { return D == 192 || D == 256 || D == 384; }
+
 // the one-accumulator form scales the weight's fp16 hi piece by 2^11: exact below 32
 bool ffn_h3_weights_ok(const float* w, long n) {
   for (long i = 0; i < n; ++i)
@@ -1159,8 +1177,11 @@ void ffn_pack_h3_host(const float* w, int rows, int cols, __bf16* out) {
 
 void launch_ffn_fused_h3(float* X, int R, int D, int F, const void* W1, const float* b1,
                          const void* W2, const float* b2, hipStream_t st, const float* byp_orig,
-                         const float* byp_scale, const float* Y) {
+                         const float* byp_scale, const float* Y, const float* Xin) {
   if (R <= 0) return;
+  if (Xin == X) Xin = nullptr;
+  ZASR_REQUIRE(Xin == nullptr || Y == nullptr, "ffn_fused_h3: out of place reads its rows from Xin");
+  if (Xin != nullptr) Y = Xin;
   if (Y == nullptr) Y = X;
   ZASR_REQUIRE(ffn_h3_supported(D, F), "ffn_fused_h3: unsupported model / feed-forward dim");
   const __bf16* w1 = reinterpret_cast<const __bf16*>(W1);
@@ -1181,13 +1202,19 @@ void launch_ffn_fused_h3(float* X, int R, int D, int F, const void* W1, const fl
   const dim3 grid(cdiv(R, rpb));
 // SB (split barriers) with one H buffer, EB (batched epilogue loads) but at d = 128: the
 // ConvNeXt instance spills with either and measured 4 % / 1.4 % slower (profiles/r06/ffn_pp/)
-#define ZASR_FFNH3(DV, TUV, NBV, NWV)                                                                \
-  if (NBV == 1 && g_ffn_split && DV != 128)                                                       \
-    ZASR_LAUNCH((ffn_wide_h3_kernel<DV, TUV, NBV, NWV, NBV == 1, DV != 128>), grid, dim3(64 * NWV), \
-                0, st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale, rpb, Y);                       \
-  else                                                                                             \
-    ZASR_LAUNCH((ffn_wide_h3_kernel<DV, TUV, NBV, NWV, false, DV != 128>), grid, dim3(64 * NWV), 0, \
-                st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale, rpb, Y)
+#define ZASR_FFNH3_(DV, TUV, NBV, NWV, OOPV)                                                          \
+  if (NBV == 1 && g_ffn_split && DV != 128)                                                           \
+    ZASR_LAUNCH((ffn_wide_h3_kernel<DV, TUV, NBV, NWV, NBV == 1, DV != 128, OOPV>), grid,              \
+                dim3(64 * NWV), 0, st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale, rpb, Y);          \
+  else                                                                                                 \
+    ZASR_LAUNCH((ffn_wide_h3_kernel<DV, TUV, NBV, NWV, false, DV != 128, OOPV>), grid, dim3(64 * NWV), \
+                0, st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale, rpb, Y)
+#define ZASR_FFNH3(DV, TUV, NBV, NWV)        \
+  if (Xin != nullptr) {                      \
+    ZASR_FFNH3_(DV, TUV, NBV, NWV, true);    \
+  } else {                                   \
+    ZASR_FFNH3_(DV, TUV, NBV, NWV, false);   \
+  }
   switch (D) {
     // tile rows (16 TUM) / H buffers: the largest tile the LDS and 256 VGPRs hold -- fewer
     // weight passes from L2 and barriers per row, for a barrier per chunk with one H buffer
@@ -1200,6 +1227,7 @@ void launch_ffn_fused_h3(float* X, int R, int D, int F, const void* W1, const fl
     default: ZASR_FFNH3(512, 3, 2, 8); break;
   }
 #undef ZASR_FFNH3
+#undef ZASR_FFNH3_
 }
 
 // D = 256 in the one-wave-per-32-tokens design compiles to one wave per SIMD (384
@@ -1236,8 +1264,9 @@ bool ffn_fused_supported(int D) {
 
 void launch_ffn_fused(float* X, int R, int D, int F, const void* W1, const float* b1,
                       const void* W2, const float* b2, hipStream_t st, const float* byp_orig,
-                      const float* byp_scale) {
+                      const float* byp_scale, const float* Xin) {
   if (R <= 0) return;
+  if (Xin == X) Xin = nullptr;
   ZASR_REQUIRE(ffn_fused_supported(D), "ffn_fused: unsupported model dim");
   ZASR_REQUIRE(F % 8 == 0, "ffn_fused: feed-forward dim must be a multiple of 8");
   const __bf16* w1 = reinterpret_cast<const __bf16*>(W1);
@@ -1257,14 +1286,23 @@ void launch_ffn_fused(float* X, int R, int D, int F, const void* W1, const float
     }
     if (D == 384 && ffn_rows_on()) {
       const int rpb = 16 * cdiv(cdiv(R, persist_blocks(cus[dev])), 16);
-      ZASR_LAUNCH((ffn_rows_kernel<384, true>), dim3(cdiv(R, rpb)), dim3(512), 0, st, X, R, F, w1, b1, w2, b2,
-                  byp_orig, byp_scale, rpb);
+      if (Xin != nullptr)
+        ZASR_LAUNCH((ffn_rows_kernel<384, true, true>), dim3(cdiv(R, rpb)), dim3(512), 0, st, X, R, F, w1,
+                    b1, w2, b2, byp_orig, byp_scale, rpb, Xin);
+      else
+        ZASR_LAUNCH((ffn_rows_kernel<384, true, false>), dim3(cdiv(R, rpb)), dim3(512), 0, st, X, R, F, w1,
+                    b1, w2, b2, byp_orig, byp_scale, rpb, Xin);
       return;
     }
 // EB (batched epilogue loads) at d = 384: 1.5-2 % (profiles/r06/ffn_pp/ffnw_eb.txt); d = 512
 // neutral, and at d = 256 it takes the kernel past 128 VGPRs (one block per CU instead of two)
-#define ZASR_FFNW(DV) \
-  ZASR_LAUNCH((ffn_wide_kernel<DV, DV == 384>), grid, dim3(512), 0, st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale)
+#define ZASR_FFNW(DV)                                                                                  \
+  if (Xin != nullptr)                                                                                  \
+    ZASR_LAUNCH((ffn_wide_kernel<DV, DV == 384, true>), grid, dim3(512), 0, st, X, R, F, w1, b1, w2, b2, \
+                byp_orig, byp_scale, Xin);                                                             \
+  else                                                                                                 \
+    ZASR_LAUNCH((ffn_wide_kernel<DV, DV == 384, false>), grid, dim3(512), 0, st, X, R, F, w1, b1, w2,  \
+                b2, byp_orig, byp_scale, Xin)
     switch (D) {
       case 256: ZASR_FFNW(256); break;
       case 384: ZASR_FFNW(384); break;
@@ -1274,7 +1312,13 @@ void launch_ffn_fused(float* X, int R, int D, int F, const void* W1, const float
     return;
   }
   const dim3 grid(cdiv(R, kTok));
-#define ZASR_FFN(DV) ZASR_LAUNCH(ffn_fused_kernel<DV>, grid, dim3(256), 0, st, X, R, F, w1, b1, w2, b2, byp_orig, byp_scale)
+#define ZASR_FFN(DV)                                                                                \
+  if (Xin != nullptr)                                                                               \
+    ZASR_LAUNCH((ffn_fused_kernel<DV, true>), grid, dim3(256), 0, st, X, R, F, w1, b1, w2, b2, byp_orig, \
+                byp_scale, Xin);                                                                    \
+  else                                                                                              \
+    ZASR_LAUNCH((ffn_fused_kernel<DV, false>), grid, dim3(256), 0, st, X, R, F, w1, b1, w2, b2,     \
+                byp_orig, byp_scale, Xin)
   switch (D) {
     case 64: ZASR_FFN(64); break;
     case 96: ZASR_FFN(96); break;

@@ -39,10 +39,12 @@ void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float
                        const float* bias, float* C);
 void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const float* b1,
                      const float* W2, const float* b2, const float* byp_orig,
-                     const float* byp_scale, float* X);
+                     const float* byp_scale, float* X, float* Xout = nullptr);
 void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, const float* W2,
                        const float* b2, const float* byp_orig, const float* byp_scale, float* X,
-                       int form);
+                       int form, float* Xout = nullptr);
+// Xout (nullable): out of place -- the kernel reads X, writes Xout (on entry the buffer's
+// initial contents); X returns what its buffer holds afterwards.  ffn_h3: Y must be null.
 
 // ---- CAM++ speaker embedding (campp_kernels.hip) ----
 struct CamppConv2d {
@@ -167,6 +169,11 @@ void launch_convnext_mlp_h3(const float* y, const float* x, long npos, const voi
 void launch_dwconv2d_tiled(const float* x, const int* L_off, const int* L_map, int total_rows,
                            const float* w, const float* b, float* out, hipStream_t st);
 
+// the fused seam against the kernels it replaces, on host operands (zasr_selftest_seam)
+void selftest_seam(int nseq, const int* L, int d, int ds, int dn, int ds_next, int c0, int ldo,
+                   const float* xd, const float* orig, const float* s, const float* wn8,
+                   const float* wo2, float* next, float* xnext, float* out, float* next_ref,
+                   float* xnext_ref, float* out_ref);
 // ---- Zipformer2 encoder elementwise / per-sequence kernels ----
 // y = x * exp(log_scale) * rsqrt(mean((x - bias)^2));  optionally y = orig + (y - orig) * s
 // copy_out (nullable): the result also written there (the next layer's bypass input; may
@@ -210,6 +217,35 @@ void launch_upsample_combine(const float* xd, const float* orig, const int* off_
 void launch_stack_glue(const float* xd, const float* orig, const int* off_in, const int* off_ds,
                        const int* map_in, int rows, int d, int ds, const float* s, float* next,
                        int dn, float* full, int ldf, int c0, hipStream_t st);
+// the same seam with its two readers folded in (seam_kernel): besides `next` it writes the next
+// stack's SimpleDownsample output and, for the seams that own columns of the full-dim output,
+// those columns of the 25 Hz encoder output directly -- what launch_stack_glue ->
+// launch_downsample(next, ds_next) -> launch_downsample(full, 2) compute, bit for bit.
+struct SeamDesc {
+  const float* xd = nullptr;    // the stack's final X at its own rate (unused when ds == 1)
+  const float* orig = nullptr;  // the stack's 50 Hz input (ds == 1: its final X)
+  const float* s = nullptr;     // out_combiner bypass scale [d] (unused when ds == 1)
+  const int* off_in = nullptr;  // 50 Hz row offsets [nseq + 1]
+  const int* off_ds = nullptr;  // the stack's own row offsets (unused when ds == 1)
+  // the level of ceil(L / G) rows, G = max(ds_next, 2): offsets, row -> sequence map, rows
+  // (ds_next >= 2: the next stack's own level; else the 25 Hz output's)
+  const int* off_run = nullptr;
+  const int* map_run = nullptr;
+  int runs = 0;
+  int rows = 0;  // 50 Hz rows
+  int d = 0, ds = 1;
+  float* next = nullptr;  // 50 Hz, width dn (truncated / zero-padded; null: none)
+  int dn = 0;
+  int ds_next = 1;                  // the next stack's factor (1: no downsample)
+  float* xnext = nullptr;           // the next stack's X [runs][dn] (ds_next >= 2)
+  const float* wn_host8 = nullptr;  // its SimpleDownsample weights (host)
+  // columns [c0, d) of the 25 Hz output (null or c0 >= d: none), row stride ldo
+  float* out = nullptr;
+  const int* off_out = nullptr;     // 25 Hz row offsets
+  const float* wo_host2 = nullptr;  // the output downsample's weights (host)
+  int ldo = 0, c0 = 0;
+};
+void launch_seam(const SeamDesc& s, hipStream_t st);
 // row -> sequence index map for one resolution (off: [nseq + 1])
 void launch_row2seq(const int* off, int nseq, int total, int* map, hipStream_t st);
 // dst[r][0:dd] = src[r][0:min(ds, dd)], zero-padded  (convert_num_channels)
@@ -345,9 +381,12 @@ void launch_attn_sa(const AttnSAArgs& a, bool online, bool bf16, hipStream_t st)
 // X[R][D] += W2 SwooshL(W1 X + b1) + b2; W1 [F][D], W2 [D][F] bf16; D in {64, 96, 128, 192, 256}
 bool ffn_fused_supported(int D);
 void ffn_pack_host(const __bf16* w, int rows, int cols, __bf16* out);
+// Xin (nullable, or X itself: in place): out of place -- X = Xin + W2 SwooshL(W1 Xin + b1) + b2,
+// the same operations in the same order, Xin left as it was; X and Xin must not overlap
 void launch_ffn_fused(float* X, int R, int D, int F, const void* W1, const float* b1,
                       const void* W2, const float* b2, hipStream_t st,
-                      const float* byp_orig = nullptr, const float* byp_scale = nullptr);
+                      const float* byp_orig = nullptr, const float* byp_scale = nullptr,
+                      const float* Xin = nullptr);
 // f16x3 mode (f32-quality products, the hidden layer on chip as fp16 pieces): W1 / W2 as
 // ffn_pack_h3_host images; D in {128, 256, 384, 512} with F % 32 == 0 or D = 192 with
 // F % 64 == 0; every |w| < 31
@@ -359,13 +398,16 @@ void ffn_h3_set_split(int on);
 void ffn_set_rows(int on);
 int ffn_rows_on();
 bool ffn_h3_weights_ok(const float* w, long n);
+// whether the out-of-place form (Xin below) costs the instantiation no registers or scratch
+bool ffn_h3_oop_ok(int D);
 void ffn_pack_h3_host(const float* w, int rows, int cols, __bf16* out);
 // Y (nullable): the rows the FFN reads when they are not X's own -- X += FFN(Y) (the ConvNeXt
-// block's pointwise MLP on the depthwise conv's output, D = 128)
+// block's pointwise MLP on the depthwise conv's output, D = 128).  Xin (nullable, or X: in
+// place; not with Y): out of place as launch_ffn_fused -- X = Xin + FFN(Xin)
 void launch_ffn_fused_h3(float* X, int R, int D, int F, const void* W1, const float* b1,
                          const void* W2, const float* b2, hipStream_t st,
                          const float* byp_orig = nullptr, const float* byp_scale = nullptr,
-                         const float* Y = nullptr);
+                         const float* Y = nullptr, const float* Xin = nullptr);
 
 // ---- transducer search (core/asr_engine.py:1023-1153) ----
 struct SearchState {

@@ -1,7 +1,8 @@
 // Kernel-level self-tests on host data (include/zasr.h zasr_selftest_*): the f16x3
 // one-accumulator kernels and the bf16 fused FFN run alone on caller-supplied operands, so the tests can sweep the
 // shapes and row counts the decode only reaches incidentally (tail tiles, M < 16, every K / D
-// and epilogue) against a float64 product on the host.  Device 0 of the process, its null
+// and epilogue) against a float64 product on the host; the fused FFNs also out of place, and
+// the fused stack seam beside the kernels it replaces.  Device 0 of the process, its null
 // stream, synchronous; nothing here is on the decode path.
 #include <cstring>
 #include <memory>
@@ -46,8 +47,9 @@ void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float
 
 void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const float* b1,
                      const float* W2, const float* b2, const float* byp_orig,
-                     const float* byp_scale, float* X) {
+                     const float* byp_scale, float* X, float* Xout) {
   ZASR_REQUIRE(R >= 1, "selftest ffn_h3: R >= 1");
+  ZASR_REQUIRE(Xout == nullptr || Y == nullptr, "selftest ffn_h3: out of place reads X");
   ZASR_REQUIRE(ffn_h3_supported(D, F), "selftest ffn_h3: unsupported model / feed-forward dim");
   ZASR_REQUIRE(ffn_h3_weights_ok(W1, (long)F * D) && ffn_h3_weights_ok(W2, (long)F * D),
                "selftest ffn_h3: |w| must stay below 31");
@@ -56,9 +58,10 @@ void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const
   ffn_pack_h3_host(W2, D, F, p2.data());
   const size_t xb = (size_t)R * D * 4;
   DevBuf dY(xb), dX(xb), d1(p1.size() * 2), d2(p2.size() * 2), db1((size_t)F * 4),
-      db2((size_t)D * 4), dbo(byp_orig ? xb : 4), dbs((size_t)D * 4);
-  up(dY, Y, xb);
+      db2((size_t)D * 4), dbo(byp_orig ? xb : 4), dbs((size_t)D * 4), dO(Xout ? xb : 4);
+  if (Y) up(dY, Y, xb);
   up(dX, X, xb);
+  if (Xout) up(dO, Xout, xb);  // what the kernel must overwrite
   up(d1, p1.data(), p1.size() * 2);
   up(d2, p2.data(), p2.size() * 2);
   up(db1, b1, (size_t)F * 4);
@@ -68,16 +71,18 @@ void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const
     up(dbo, byp_orig, xb);
     up(dbs, byp_scale, (size_t)D * 4);
   }
-  launch_ffn_fused_h3(dX.as<float>(), R, D, F, d1.p, db1.as<float>(), d2.p, db2.as<float>(),
-                      nullptr, byp_orig ? dbo.as<float>() : nullptr,
-                      byp_orig ? dbs.as<float>() : nullptr, dY.as<float>());
+  launch_ffn_fused_h3(Xout ? dO.as<float>() : dX.as<float>(), R, D, F, d1.p, db1.as<float>(), d2.p,
+                      db2.as<float>(), nullptr, byp_orig ? dbo.as<float>() : nullptr,
+                      byp_orig ? dbs.as<float>() : nullptr, Y ? dY.as<float>() : nullptr,
+                      Xout ? dX.as<float>() : nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   ZASR_HIP_CHECK(hipMemcpy(X, dX.p, xb, hipMemcpyDeviceToHost));
+  if (Xout) ZASR_HIP_CHECK(hipMemcpy(Xout, dO.p, xb, hipMemcpyDeviceToHost));
 }
 
 void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, const float* W2,
                        const float* b2, const float* byp_orig, const float* byp_scale, float* X,
-                       int form) {
+                       int form, float* Xout) {
   ZASR_REQUIRE(form == 0 || form == 1, "selftest ffn_bf16: form 0 (default route) or 1 (rows form)");
   ZASR_REQUIRE(R >= 1, "selftest ffn_bf16: R >= 1");
   ZASR_REQUIRE(ffn_fused_supported(D), "selftest ffn_bf16: unsupported model dim");
@@ -94,8 +99,9 @@ void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, co
   }
   const size_t xb = (size_t)R * D * 4;
   DevBuf dX(xb), d1(h1.size() * 2), d2(h2.size() * 2), db1((size_t)F * 4), db2((size_t)D * 4),
-      dbo(byp_orig ? xb : 4), dbs((size_t)D * 4);
+      dbo(byp_orig ? xb : 4), dbs((size_t)D * 4), dO(Xout ? xb : 4);
   up(dX, X, xb);
+  if (Xout) up(dO, Xout, xb);  // what the kernel must overwrite
   up(d1, h1.data(), h1.size() * 2);
   up(d2, h2.data(), h2.size() * 2);
   up(db1, b1, (size_t)F * 4);
@@ -108,8 +114,9 @@ void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, co
   const int saved = ffn_rows_on();
   ffn_set_rows(form);
   try {
-    launch_ffn_fused(dX.as<float>(), R, D, F, d1.p, db1.as<float>(), d2.p, db2.as<float>(), nullptr,
-                     byp_orig ? dbo.as<float>() : nullptr, byp_orig ? dbs.as<float>() : nullptr);
+    launch_ffn_fused(Xout ? dO.as<float>() : dX.as<float>(), R, D, F, d1.p, db1.as<float>(), d2.p,
+                     db2.as<float>(), nullptr, byp_orig ? dbo.as<float>() : nullptr,
+                     byp_orig ? dbs.as<float>() : nullptr, Xout ? dX.as<float>() : nullptr);
   } catch (...) {
     ffn_set_rows(saved);
     throw;
@@ -117,6 +124,106 @@ void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, co
   ffn_set_rows(saved);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   ZASR_HIP_CHECK(hipMemcpy(X, dX.p, xb, hipMemcpyDeviceToHost));
+  if (Xout) ZASR_HIP_CHECK(hipMemcpy(Xout, dO.p, xb, hipMemcpyDeviceToHost));
+}
+
+void selftest_seam(int nseq, const int* L, int d, int ds, int dn, int ds_next, int c0, int ldo,
+                   const float* xd, const float* orig, const float* s, const float* wn8,
+                   const float* wo2, float* next, float* xnext, float* out, float* next_ref,
+                   float* xnext_ref, float* out_ref) {
+  ZASR_REQUIRE(nseq >= 1 && d >= 4 && dn >= 0 && ds >= 1 && ds_next >= 1 && c0 >= 0,
+               "selftest seam: sizes");
+  ZASR_REQUIRE(ldo % 4 == 0 && ldo >= d, "selftest seam: output row stride >= d, a multiple of 4");
+  const bool has_x = ds_next > 1 && dn > 0, has_out = c0 < d;
+  // the levels the engine forms: 50 Hz, the stack's own, the next stack's, the 25 Hz output
+  auto level = [&](int f, std::vector<int>& off) {
+    off.assign(nseq + 1, 0);
+    for (int b = 0; b < nseq; ++b) {
+      ZASR_REQUIRE(L[b] >= 1, "selftest seam: every sequence needs a frame");
+      off[b + 1] = off[b] + (L[b] + f - 1) / f;
+    }
+    return off[nseq];
+  };
+  std::vector<int> oL, oS, oN, oO;
+  const int rows = level(1, oL), rs = level(ds, oS), rn = level(ds_next, oN), ro = level(2, oO);
+  const size_t ib = (size_t)(nseq + 1) * 4;
+  DevBuf dL(ib), dS(ib), dN(ib), dO(ib), mL((size_t)rows * 4), mN((size_t)rn * 4),
+      mO((size_t)ro * 4);
+  up(dL, oL.data(), ib);
+  up(dS, oS.data(), ib);
+  up(dN, oN.data(), ib);
+  up(dO, oO.data(), ib);
+  launch_row2seq(dL.as<int>(), nseq, rows, mL.as<int>(), nullptr);
+  launch_row2seq(dN.as<int>(), nseq, rn, mN.as<int>(), nullptr);
+  launch_row2seq(dO.as<int>(), nseq, ro, mO.as<int>(), nullptr);
+  const size_t bo = (size_t)rows * d * 4, bx = (size_t)rs * d * 4, bn = (size_t)rows * dn * 4,
+               bxn = (size_t)rn * dn * 4, bout = (size_t)ro * ldo * 4, bfull = (size_t)rows * ldo * 4;
+  DevBuf dorig(bo), dxd(bx), ds_(d * 4), dnext(bn), dxn(bxn), dout(bout), dnext_r(bn), dxn_r(bxn),
+      dout_r(bout), dfull(bfull);
+  up(dorig, orig, bo);
+  if (ds > 1) {
+    up(dxd, xd, bx);
+    up(ds_, s, (size_t)d * 4);
+  }
+  // both sides start from the caller's images, so what a kernel leaves alone shows
+  up(dnext, next, bn);
+  up(dnext_r, next, bn);
+  if (has_x) {
+    up(dxn, xnext, bxn);
+    up(dxn_r, xnext, bxn);
+  }
+  up(dout, out, bout);
+  up(dout_r, out, bout);
+  ZASR_HIP_CHECK(hipMemset(dfull.p, 0, bfull > 0 ? bfull : 4));
+  SeamDesc sd;
+  sd.xd = dxd.as<float>();
+  sd.orig = dorig.as<float>();
+  sd.s = ds_.as<float>();
+  sd.off_in = dL.as<int>();
+  sd.off_ds = dS.as<int>();
+  sd.off_run = ds_next > 1 ? dN.as<int>() : dO.as<int>();
+  sd.map_run = ds_next > 1 ? mN.as<int>() : mO.as<int>();
+  sd.runs = ds_next > 1 ? rn : ro;
+  sd.rows = rows;
+  sd.d = d;
+  sd.ds = ds;
+  sd.next = dn > 0 ? dnext.as<float>() : nullptr;
+  sd.dn = dn;
+  sd.ds_next = ds_next;
+  if (has_x) {
+    sd.xnext = dxn.as<float>();
+    sd.wn_host8 = wn8;
+  }
+  if (has_out) {
+    sd.out = dout.as<float>();
+    sd.off_out = dO.as<int>();
+    sd.wo_host2 = wo2;
+    sd.ldo = ldo;
+    sd.c0 = c0;
+  }
+  launch_seam(sd, nullptr);
+  // the composition it replaces: glue -> downsample(next) -> downsample(full, 2)
+  launch_stack_glue(dxd.as<float>(), dorig.as<float>(), dL.as<int>(), dS.as<int>(), mL.as<int>(),
+                    rows, d, ds, ds_.as<float>(), dn > 0 ? dnext_r.as<float>() : nullptr, dn,
+                    has_out ? dfull.as<float>() : nullptr, ldo, c0, nullptr);
+  if (has_x)
+    launch_downsample(dnext_r.as<float>(), dL.as<int>(), dN.as<int>(), mN.as<int>(), rn, dn,
+                      ds_next, wn8, dxn_r.as<float>(), nullptr);
+  if (has_out)
+    launch_downsample(dfull.as<float>(), dL.as<int>(), dO.as<int>(), mO.as<int>(), ro, ldo, 2, wo2,
+                      dout_r.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  auto down = [](void* h, const DevBuf& dv, size_t bytes) {
+    if (bytes) ZASR_HIP_CHECK(hipMemcpy(h, dv.p, bytes, hipMemcpyDeviceToHost));
+  };
+  down(next, dnext, bn);
+  down(next_ref, dnext_r, bn);
+  if (has_x) {
+    down(xnext, dxn, bxn);
+    down(xnext_ref, dxn_r, bxn);
+  }
+  down(out, dout, bout);
+  down(out_ref, dout_r, bout);
 }
 
 }  // namespace zasr

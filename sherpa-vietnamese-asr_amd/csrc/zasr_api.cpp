@@ -694,6 +694,41 @@ int zasr_selftest_ffn_bf16(int32_t R, int32_t D, int32_t F, const float* W1, con
   });
 }
 
+int zasr_selftest_ffn_bf16_oop(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
+                               const float* W2, const float* b2, const float* byp_orig,
+                               const float* byp_scale, float* X, float* Xout, int32_t form) {
+  if (!W1 || !b1 || !W2 || !b2 || !X || !Xout) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_ffn_bf16(R, D, F, W1, b1, W2, b2, byp_orig, byp_scale, X, form, Xout);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_ffn_h3_oop(int32_t R, int32_t D, int32_t F, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* byp_orig,
+                             const float* byp_scale, float* X, float* Xout) {
+  if (!W1 || !b1 || !W2 || !b2 || !X || !Xout) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_ffn_h3(R, D, F, nullptr, W1, b1, W2, b2, byp_orig, byp_scale, X, Xout);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seam(int32_t nseq, const int32_t* L, int32_t d, int32_t ds, int32_t dn,
+                       int32_t ds_next, int32_t c0, int32_t ldo, const float* xd,
+                       const float* orig, const float* s, const float* wn8, const float* wo2,
+                       float* next, float* xnext, float* out, float* next_ref, float* xnext_ref,
+                       float* out_ref) {
+  if (!L || !orig || !wn8 || !wo2 || !next || !xnext || !out || !next_ref || !xnext_ref ||
+      !out_ref || (ds > 1 && (!xd || !s)))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seam(nseq, L, d, ds, dn, ds_next, c0, ldo, xd, orig, s, wn8, wo2, next, xnext,
+                        out, next_ref, xnext_ref, out_ref);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
                                  int32_t order, uint32_t* out, int64_t cap, int32_t* grid) {
   if (!lens || !grid || (cap > 0 && !out) || cap < 0) return fail(ZASR_ERR_INVALID, "null argument");

@@ -36,7 +36,8 @@ EXPORTS = (
     "zasr_stream_result_json", "zasr_set_tokens", "zasr_model_routes",
     "zasr_fbank_set_mel_banks", "zasr_selftest_launch", "zasr_decode_host_batches",
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
-    "zasr_selftest_attn_block_map",
+    "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
+    "zasr_selftest_ffn_h3_oop",
 )
 
 
@@ -223,6 +224,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_attn_block_map.argtypes = [C.POINTER(I32), I32, I32, I32,
                                                  C.POINTER(C.c_uint32), I64, C.POINTER(I32)]
     lib.zasr_selftest_attn_block_map.restype = C.c_int
+    lib.zasr_selftest_seam.argtypes = [I32, C.POINTER(I32)] + [I32] * 6 + [fp] * 11
+    lib.zasr_selftest_seam.restype = C.c_int
+    lib.zasr_selftest_ffn_bf16_oop.argtypes = [I32, I32, I32] + [fp] * 8 + [I32]
+    lib.zasr_selftest_ffn_bf16_oop.restype = C.c_int
+    lib.zasr_selftest_ffn_h3_oop.argtypes = [I32, I32, I32] + [fp] * 8
+    lib.zasr_selftest_ffn_h3_oop.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -333,6 +340,61 @@ def selftest_attn_block_map(lens, units_per_seq: int, order: int = 0,
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return out[:grid.value].copy()
+
+
+def selftest_ffn_oop(kind: str, W1, b1, W2, b2, X, byp_orig=None, byp_scale=None, form: int = 0,
+                     fill: float = -777.25, lib_path: Optional[str] = None):
+    """A fused FFN out of place on host operands (zasr_selftest_ffn_bf16_oop, kind "bf16", or
+    zasr_selftest_ffn_h3_oop, kind "h3"): returns (the output buffer, which started as `fill`,
+    the input buffer after the call)."""
+    lib = load_library(lib_path)
+    W1, b1, W2, b2, X = (_f32(v) for v in (W1, b1, W2, b2, X))
+    X = X.copy()
+    out = np.full(X.shape, fill, dtype=np.float32)
+    bo = None if byp_orig is None else _f32(byp_orig)
+    bs = None if byp_scale is None else _f32(byp_scale)
+    p = lambda x: None if x is None else x.ctypes.data_as(C_FP)
+    args = (X.shape[0], X.shape[1], W1.shape[0], p(W1), p(b1), p(W2), p(b2), p(bo), p(bs), p(X),
+            p(out))
+    if kind == "bf16":
+        rc = lib.zasr_selftest_ffn_bf16_oop(*args, int(form))
+    elif kind == "h3":
+        rc = lib.zasr_selftest_ffn_h3_oop(*args)
+    else:
+        raise ValueError(kind)
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out, X
+
+
+def selftest_seam(L, d: int, ds: int, dn: int, ds_next: int, c0: int, ldo: int, xd, orig, s,
+                  wn8, wo2, fill: float = -777.25, lib_path: Optional[str] = None) -> dict:
+    """The fused stack seam and the glue -> downsample -> downsample composition it replaces on
+    the same host operands (zasr_selftest_seam).  Every destination starts as `fill`; returns
+    {"next", "xnext", "out"} (fused) and {"next_ref", "xnext_ref", "out_ref"} (composition):
+    next [sum L][dn], xnext [sum ceil(L / ds_next)][dn], out [sum ceil(L / 2)][ldo]."""
+    lib = load_library(lib_path)
+    L = np.ascontiguousarray(L, dtype=np.int32)
+    orig, wn8, wo2 = _f32(orig), _f32(wn8), _f32(wo2)
+    xd = None if xd is None else _f32(xd)
+    s = None if s is None else _f32(s)
+    rows = int(L.sum())
+    rn = int(((L + ds_next - 1) // ds_next).sum())
+    ro = int(((L + 1) // 2).sum())
+    assert orig.shape == (rows, d) and wn8.shape == (8,) and wo2.shape == (2,)
+    assert ds == 1 or (xd.shape == (int(((L + ds - 1) // ds).sum()), d) and s.shape == (d,))
+    res = {}
+    for name, shape in (("next", (rows, dn)), ("xnext", (rn, dn)), ("out", (ro, ldo))):
+        for k in (name, name + "_ref"):
+            res[k] = np.full(shape, fill, dtype=np.float32)
+    p = lambda x: None if x is None else x.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_seam(len(L), L.ctypes.data_as(C.POINTER(C.c_int32)), int(d), int(ds),
+                                int(dn), int(ds_next), int(c0), int(ldo), p(xd), p(orig), p(s),
+                                p(wn8), p(wo2), p(res["next"]), p(res["xnext"]), p(res["out"]),
+                                p(res["next_ref"]), p(res["xnext_ref"]), p(res["out_ref"]))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return res
 
 
 def silence_flags(d_wav_ptr: int, n: int, frame_len: int, threshold: float, d_flags_ptr: int,
