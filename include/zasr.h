@@ -30,6 +30,14 @@
  *   zasr_result_*          the (token_ids, frames, ys_log_probs, T, emit_logits) tuple of
  *                          core/asr_engine.py:1153 (entropy statistics instead of raw
  *                          logits rows, reduced on device); SherpaOnnxGetOfflineStreamResult
+ *   zasr_audio_to_16k      load_audio's decode / downmix / resample, core/asr_engine.py:492-508
+ *                          (ffmpeg + soxr there; sherpa-onnx's LinearResample definition here)
+ *   zasr_audio_peak, zasr_audio_scale
+ *                          the quiet-file boost, core/asr_engine.py:512-516, and
+ *                          adaptive_peak_limit, core/audio_preprocessing.py:226-243
+ *   zasr_audio_segment_sumsq, zasr_audio_apply_gain
+ *                          per_segment_rms_normalize, core/audio_preprocessing.py:46-140 (the
+ *                          gain plan itself stays host logic, zasr/audio.py)
  */
 #ifndef ZASR_H_
 #define ZASR_H_
@@ -309,6 +317,65 @@ int32_t zasr_vad_last_passes(const zasr_vad* h);
    prob [n], state_out [2][n][128] (the ORT session surface, vad_utils.py:100-102) */
 int zasr_vad_window(zasr_vad* h, const float* input, const float* state, int32_t n, float* prob,
                     float* state_out);
+
+/* ---- device audio front end --------------------------------------------------------------
+   Raw PCM -> the 16 kHz mono float32 HBM signal that zasr_decode_device,
+   zasr_vad_probs_device and zasr_campp_windows_device read, and the reference's level
+   conditioning on that signal.  The handle caches one polyphase table per input rate and owns
+   the pinned staging buffers of host sources.  Every entry point with a `stream` is ordered
+   after the stream's earlier work; those that return a value to the host synchronise it.
+   Results are bit-identical from run to run (no floating-point atomics anywhere). */
+typedef struct zasr_audio zasr_audio;
+enum { ZASR_AUDIO_F32 = 0, ZASR_AUDIO_I16 = 1 };
+int zasr_audio_create(int32_t device_id, zasr_audio** out);
+void zasr_audio_destroy(zasr_audio* h);
+/* Host-only.  Samples zasr_audio_to_16k makes of n_frames frames at `rate`:
+   ceil(n_frames * 16000 / rate) in integers; -1 for a rate outside 4000..384000. */
+int64_t zasr_audio_out_len(int32_t rate, int64_t n_frames);
+/* Host-only (no GPU): the polyphase table of `rate`.  With g = gcd(rate, 16000), P = 16000 / g,
+   Q = rate / g, output m = q P + p is sum_t x[q Q + lo[p] + t] * w[p * taps + t], t < taps,
+   x = 0 outside the signal: the Hann-windowed sinc of sherpa-onnx's LinearResample (the
+   resampler behind OfflineStream::AcceptWaveform, which the reference's stream callers rely on;
+   its file loader resamples with ffmpeg, core/asr_engine.py:501-508) with the 1 / rate factor
+   folded in.  lo [P] and w [P * taps] (cap = elements of w) may both be NULL to read the sizes
+   first.  out_tile / in_tile (nullable): outputs one workgroup makes per tile, and the input
+   frames that many outputs span. */
+int zasr_audio_resample_taps(int32_t rate, int32_t* P, int32_t* Q, int32_t* taps,
+                             int32_t* out_tile, int32_t* in_tile, int32_t* lo, float* w,
+                             int64_t cap);
+/* Convert (int16 -> x * 2^-15, soundfile's dtype='float32' read), downmix (the mean over
+   channels in float32, audio.mean(axis=1), core/asr_engine.py:497-500) and resample to 16 kHz
+   in one pass: src holds n_frames frames of `channels` interleaved samples (1..8) of `format`
+   at `rate` Hz (4000..384000), on the host (src_on_device 0: uploaded in bounded pinned pieces
+   under the kernel) or on the device.  d_out (device, cap samples) receives *n_out =
+   zasr_audio_out_len samples.  rate 16000 runs no filter: mono float32 is copied bit for bit.
+   Replaces load_audio's decode-side work, core/asr_engine.py:492-508. */
+int zasr_audio_to_16k(zasr_audio* h, const void* src, int32_t format, int32_t channels,
+                      int32_t rate, int64_t n_frames, int32_t src_on_device, float* d_out,
+                      int64_t cap, int64_t* n_out, void* stream);
+/* *peak = max |d_wav[i]| (np.max(np.abs(audio)), core/asr_engine.py:513,
+   core/audio_preprocessing.py:239); 0 for n = 0. */
+int zasr_audio_peak(zasr_audio* h, const float* d_wav, int64_t n, float* peak, void* stream);
+/* d_wav[i] = (d_wav[i] / divisor) * multiplier, two float32 roundings: the quiet-file boost
+   audio / peak * 0.95 (core/asr_engine.py:514-515) with (peak, 0.95f), and the peak limiter
+   audio * (0.95 / peak) (core/audio_preprocessing.py:240-241) with (1, 0.95f / peak). */
+int zasr_audio_scale(zasr_audio* h, float* d_wav, int64_t n, float divisor, float multiplier,
+                     void* stream);
+/* out[s] = sum of d_wav[i]^2 over [seg_begin[s], seg_end[s]) in float64 (host array), all
+   segments in one launch; segments must lie inside [0, n).  The device half of
+   compute_segment_rms (core/audio_preprocessing.py:39-43, :76-83). */
+int zasr_audio_segment_sumsq(zasr_audio* h, const float* d_wav, int64_t n,
+                             const int64_t* seg_begin, const int64_t* seg_end, int32_t n_seg,
+                             double* out, void* stream);
+/* d_wav[i] *= gain(i) and *peak = max |result|, one pass.  The gain is 1 except on the
+   pieces [piece_begin[k], piece_end[k]) (ascending, disjoint): piece_gain[k] where
+   piece_ramp[k] < 0, else ramp_values[piece_ramp[k] + i - piece_begin[k]].  Applies the sparse
+   form of the reference's gain_map (core/audio_preprocessing.py:100-129) and takes the
+   limiter's peak (:239); n_pieces 0 is the peak alone. */
+int zasr_audio_apply_gain(zasr_audio* h, float* d_wav, int64_t n, const int64_t* piece_begin,
+                          const int64_t* piece_end, const float* piece_gain,
+                          const int64_t* piece_ramp, int32_t n_pieces, const float* ramp_values,
+                          int64_t n_ramp_values, float* peak, void* stream);
 
 /* model facts */
 int32_t zasr_vocab_size(const zasr_recognizer* h);

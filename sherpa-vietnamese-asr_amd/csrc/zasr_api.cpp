@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/zasr.h"
+#include "audio.h"
 #include "campp.h"
 #include "common.h"
 #include "vad.h"
@@ -56,6 +57,10 @@ struct zasr_vibert {
 
 struct zasr_vad {
   std::unique_ptr<zasr::VadEngine> eng;
+};
+
+struct zasr_audio {
+  std::unique_ptr<zasr::AudioFrontEnd> eng;
 };
 
 namespace {
@@ -747,6 +752,150 @@ int zasr_silence_flags(const float* d_wav, int64_t n, int32_t frame_len, float t
   return guarded([&]() {
     zasr::launch_silence_flags(d_wav, (long)n, (int)frame_len, threshold, d_flags,
                                reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+// ---- device audio front end (audio.h) ----
+namespace {
+int audio_source_error(int32_t format, int32_t channels, int32_t rate) {
+  if (format != ZASR_AUDIO_F32 && format != ZASR_AUDIO_I16)
+    return fail(ZASR_ERR_INVALID, "format must be ZASR_AUDIO_F32 or ZASR_AUDIO_I16");
+  if (channels < 1 || channels > zasr::kAudioMaxChannels)
+    return fail(ZASR_ERR_INVALID, "channels must be in 1..8");
+  if (rate < zasr::kAudioMinRate || rate > zasr::kAudioMaxRate)
+    return fail(ZASR_ERR_INVALID, "sample rate must be in 4000..384000");
+  return ZASR_OK;
+}
+}  // namespace
+
+int zasr_audio_create(int32_t device_id, zasr_audio** out) {
+  if (!out) return fail(ZASR_ERR_INVALID, "null out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_audio;
+    try {
+      h->eng.reset(new zasr::AudioFrontEnd(device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_audio_destroy(zasr_audio* h) { delete h; }
+
+int64_t zasr_audio_out_len(int32_t rate, int64_t n_frames) {
+  if (rate < zasr::kAudioMinRate || rate > zasr::kAudioMaxRate || n_frames < 0 ||
+      n_frames > (int64_t(1) << 40)) {
+    fail(ZASR_ERR_INVALID, "sample rate must be in 4000..384000 and n_frames in 0..2^40");
+    return -1;
+  }
+  return zasr::audio_out_len(rate, (long)n_frames);
+}
+
+int zasr_audio_resample_taps(int32_t rate, int32_t* P, int32_t* Q, int32_t* taps,
+                             int32_t* out_tile, int32_t* in_tile, int32_t* lo, float* w,
+                             int64_t cap) {
+  if (!P || !Q || !taps) return fail(ZASR_ERR_INVALID, "null argument");
+  if (rate < zasr::kAudioMinRate || rate > zasr::kAudioMaxRate)
+    return fail(ZASR_ERR_INVALID, "sample rate must be in 4000..384000");
+  return guarded([&]() {
+    const zasr::ResampleTable t = zasr::make_resample_table(rate);
+    *P = t.P;
+    *Q = t.Q;
+    *taps = t.taps;
+    if (out_tile) *out_tile = t.out_tile;
+    if (in_tile) *in_tile = t.in_tile();
+    if (lo || w) {
+      if (cap < (int64_t)t.w.size() || !lo || !w)
+        return fail(ZASR_ERR_INVALID, "table buffers too small (lo [P], w [P * taps] = cap)");
+      std::memcpy(lo, t.lo.data(), t.lo.size() * sizeof(int32_t));
+      std::memcpy(w, t.w.data(), t.w.size() * sizeof(float));
+    }
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_audio_to_16k(zasr_audio* h, const void* src, int32_t format, int32_t channels,
+                      int32_t rate, int64_t n_frames, int32_t src_on_device, float* d_out,
+                      int64_t cap, int64_t* n_out, void* stream) {
+  if (const int rc = audio_source_error(format, channels, rate)) return rc;
+  if (!h || !n_out || n_frames < 0 || (n_frames > 0 && (!src || !d_out)))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  if (n_frames > (int64_t(1) << 40)) return fail(ZASR_ERR_INVALID, "n_frames too large");
+  if (zasr::audio_out_len(rate, (long)n_frames) > cap)
+    return fail(ZASR_ERR_INVALID, "output buffer too small (zasr_audio_out_len samples needed)");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    *n_out = h->eng->to_16k(src, format, channels, rate, (long)n_frames, src_on_device != 0, d_out,
+                            (long)cap, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_audio_peak(zasr_audio* h, const float* d_wav, int64_t n, float* peak, void* stream) {
+  if (!h || !peak || n < 0 || (n > 0 && !d_wav)) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    *peak = h->eng->peak(d_wav, (long)n, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_audio_scale(zasr_audio* h, float* d_wav, int64_t n, float divisor, float multiplier,
+                     void* stream) {
+  if (!h || n < 0 || (n > 0 && !d_wav)) return fail(ZASR_ERR_INVALID, "null argument");
+  if (!(divisor != 0.f)) return fail(ZASR_ERR_INVALID, "divisor must not be 0");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->scale(d_wav, (long)n, divisor, multiplier, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_audio_segment_sumsq(zasr_audio* h, const float* d_wav, int64_t n,
+                             const int64_t* seg_begin, const int64_t* seg_end, int32_t n_seg,
+                             double* out, void* stream) {
+  if (!h || n < 0 || n_seg < 0 || (n_seg > 0 && (!seg_begin || !seg_end || !out)) ||
+      (n > 0 && !d_wav))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  for (int32_t s = 0; s < n_seg; ++s)
+    if (seg_begin[s] < 0 || seg_end[s] < seg_begin[s] || seg_end[s] > n)
+      return fail(ZASR_ERR_INVALID, "segment outside the signal");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->segment_sumsq(d_wav, reinterpret_cast<const long*>(seg_begin),
+                          reinterpret_cast<const long*>(seg_end), n_seg, out,
+                          reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_audio_apply_gain(zasr_audio* h, float* d_wav, int64_t n, const int64_t* piece_begin,
+                          const int64_t* piece_end, const float* piece_gain,
+                          const int64_t* piece_ramp, int32_t n_pieces, const float* ramp_values,
+                          int64_t n_ramp_values, float* peak, void* stream) {
+  if (!h || !peak || n < 0 || n_pieces < 0 || n_ramp_values < 0 || (n > 0 && !d_wav) ||
+      (n_pieces > 0 && (!piece_begin || !piece_end || !piece_gain || !piece_ramp)) ||
+      (n_ramp_values > 0 && !ramp_values))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  int64_t prev = 0;
+  for (int32_t k = 0; k < n_pieces; ++k) {
+    if (piece_begin[k] < prev || piece_end[k] <= piece_begin[k] || piece_end[k] > n)
+      return fail(ZASR_ERR_INVALID, "pieces must be non-empty, ascending, disjoint and inside the signal");
+    if (piece_ramp[k] >= 0 && piece_ramp[k] + (piece_end[k] - piece_begin[k]) > n_ramp_values)
+      return fail(ZASR_ERR_INVALID, "ramp piece reaches past ramp_values");
+    prev = piece_end[k];
+  }
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    *peak = h->eng->apply_gain(d_wav, (long)n, reinterpret_cast<const long*>(piece_begin),
+                               reinterpret_cast<const long*>(piece_end), piece_gain,
+                               reinterpret_cast<const long*>(piece_ramp), n_pieces, ramp_values,
+                               (long)n_ramp_values, reinterpret_cast<hipStream_t>(stream));
     return (int)ZASR_OK;
   });
 }

@@ -38,6 +38,9 @@ EXPORTS = (
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
     "zasr_selftest_ffn_h3_oop",
+    "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
+    "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
+    "zasr_audio_apply_gain",
 )
 
 
@@ -230,6 +233,25 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_ffn_bf16_oop.restype = C.c_int
     lib.zasr_selftest_ffn_h3_oop.argtypes = [I32, I32, I32] + [fp] * 8
     lib.zasr_selftest_ffn_h3_oop.restype = C.c_int
+    # device audio front end (zasr/audio.py)
+    lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
+    lib.zasr_audio_create.restype = C.c_int
+    lib.zasr_audio_destroy.argtypes = [P]
+    lib.zasr_audio_destroy.restype = None
+    lib.zasr_audio_out_len.argtypes = [I32, I64]
+    lib.zasr_audio_out_len.restype = I64
+    lib.zasr_audio_resample_taps.argtypes = [I32, i32p, i32p, i32p, i32p, i32p, i32p, fp, I64]
+    lib.zasr_audio_resample_taps.restype = C.c_int
+    lib.zasr_audio_to_16k.argtypes = [P, P, I32, I32, I32, I64, I32, P, I64, i64p, P]
+    lib.zasr_audio_to_16k.restype = C.c_int
+    lib.zasr_audio_peak.argtypes = [P, P, I64, fp, P]
+    lib.zasr_audio_peak.restype = C.c_int
+    lib.zasr_audio_scale.argtypes = [P, P, I64, C.c_float, C.c_float, P]
+    lib.zasr_audio_scale.restype = C.c_int
+    lib.zasr_audio_segment_sumsq.argtypes = [P, P, I64, i64p, i64p, I32, C.POINTER(C.c_double), P]
+    lib.zasr_audio_segment_sumsq.restype = C.c_int
+    lib.zasr_audio_apply_gain.argtypes = [P, P, I64, i64p, i64p, fp, i64p, I32, fp, I64, fp, P]
+    lib.zasr_audio_apply_gain.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -891,3 +913,132 @@ class VadSession:
                                              st.ctypes.data_as(fp), n, p.ctypes.data_as(fp),
                                              so.ctypes.data_as(fp)))
         return [p[:, None], so]
+
+
+AUDIO_FORMATS = {"float32": 0, "int16": 1}  # include/zasr.h ZASR_AUDIO_F32 / ZASR_AUDIO_I16
+
+
+def audio_out_len(sample_rate: int, n_frames: int, lib_path: Optional[str] = None) -> int:
+    """Samples the front end makes of n_frames frames at sample_rate (zasr_audio_out_len,
+    host only): ceil(n_frames * 16000 / sample_rate)."""
+    lib = load_library(lib_path)
+    n = int(lib.zasr_audio_out_len(int(sample_rate), int(n_frames)))
+    if n < 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return n
+
+
+def audio_resample_taps(sample_rate: int, lib_path: Optional[str] = None) -> dict:
+    """The front end's polyphase table of one input rate (zasr_audio_resample_taps, host only):
+    {"P", "Q", "taps", "out_tile", "in_tile", "lo" int32 [P], "w" float32 [P, taps]}."""
+    lib = load_library(lib_path)
+    v = [C.c_int32() for _ in range(5)]
+    refs = [C.byref(x) for x in v]
+    if lib.zasr_audio_resample_taps(int(sample_rate), *refs, None, None, 0) != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    Pn, Q, taps, out_tile, in_tile = (x.value for x in v)
+    lo = np.empty(Pn, np.int32)
+    w = np.empty((Pn, taps), np.float32)
+    if lib.zasr_audio_resample_taps(int(sample_rate), *refs,
+                                    lo.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    w.ctypes.data_as(C_FP), w.size) != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return {"P": Pn, "Q": Q, "taps": taps, "out_tile": out_tile, "in_tile": in_tile,
+            "lo": lo, "w": w}
+
+
+class AudioFrontEnd:
+    """The device audio front end (include/zasr.h zasr_audio_*): raw PCM to the 16 kHz mono
+    float32 signal in HBM, and the level passes of the reference's load_audio boost and
+    preprocess_audio on that signal.  Signals and outputs are device pointers (ints); a PCM
+    source is a numpy array (host) or a device pointer.  zasr/audio.py is the numpy / torch
+    surface over this class."""
+
+    def __init__(self, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        if self.lib.zasr_audio_create(int(device_id), C.byref(h)) != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+        self.handle = h
+        self.device_id = int(device_id)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_audio_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def to_16k(self, src, sample_rate: int, d_out: int, cap: int, channels: int = 1,
+               n_frames: Optional[int] = None, fmt: Optional[str] = None,
+               stream: int = 0) -> int:
+        """src: a C-contiguous numpy array [n] or [n, C] of float32 / int16 (host source), or
+        a device pointer with n_frames, channels and fmt ("float32" | "int16").  Writes the
+        16 kHz signal at device pointer d_out (cap samples); returns its length."""
+        if isinstance(src, np.ndarray):
+            if src.dtype.name not in AUDIO_FORMATS or src.ndim not in (1, 2):
+                raise ValueError("samples must be float32 or int16, shaped [n] or [n, channels]")
+            keep = np.ascontiguousarray(src)
+            n_frames, channels = keep.shape[0], (keep.shape[1] if keep.ndim == 2 else 1)
+            fmt, ptr, on_device = keep.dtype.name, keep.ctypes.data, 0
+        else:
+            if n_frames is None or fmt not in AUDIO_FORMATS:
+                raise ValueError("a device source needs n_frames and fmt")
+            keep, ptr, on_device = None, int(src), 1
+        n_out = C.c_int64()
+        self._check(self.lib.zasr_audio_to_16k(
+            self.handle, C.c_void_p(ptr), AUDIO_FORMATS[fmt], int(channels), int(sample_rate),
+            int(n_frames), on_device, C.c_void_p(d_out), int(cap), C.byref(n_out),
+            C.c_void_p(stream)))
+        del keep
+        return int(n_out.value)
+
+    def peak(self, d_wav: int, n: int, stream: int = 0) -> np.float32:
+        v = C.c_float()
+        self._check(self.lib.zasr_audio_peak(self.handle, C.c_void_p(d_wav), int(n), C.byref(v),
+                                             C.c_void_p(stream)))
+        return np.float32(v.value)
+
+    def scale(self, d_wav: int, n: int, divisor, multiplier, stream: int = 0) -> None:
+        """d_wav = (d_wav / divisor) * multiplier in float32."""
+        self._check(self.lib.zasr_audio_scale(self.handle, C.c_void_p(d_wav), int(n),
+                                              float(np.float32(divisor)),
+                                              float(np.float32(multiplier)), C.c_void_p(stream)))
+
+    def segment_sumsq(self, d_wav: int, n: int, seg_begin, seg_end, stream: int = 0) -> np.ndarray:
+        b = np.ascontiguousarray(seg_begin, np.int64)
+        e = np.ascontiguousarray(seg_end, np.int64)
+        if b.shape != e.shape or b.ndim != 1:
+            raise ValueError("seg_begin and seg_end differ in length")
+        out = np.zeros(b.size, np.float64)
+        i64 = C.POINTER(C.c_int64)
+        self._check(self.lib.zasr_audio_segment_sumsq(
+            self.handle, C.c_void_p(d_wav), int(n), b.ctypes.data_as(i64), e.ctypes.data_as(i64),
+            b.size, out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)))
+        return out
+
+    def apply_gain(self, d_wav: int, n: int, piece_begin, piece_end, piece_gain, piece_ramp,
+                   ramp_values, stream: int = 0) -> np.float32:
+        """d_wav *= the sparse gain plan (zasr_audio_apply_gain); returns max |result|."""
+        pb = np.ascontiguousarray(piece_begin, np.int64)
+        pe = np.ascontiguousarray(piece_end, np.int64)
+        pg = np.ascontiguousarray(piece_gain, np.float32)
+        po = np.ascontiguousarray(piece_ramp, np.int64)
+        rv = np.ascontiguousarray(ramp_values, np.float32)
+        if not (pb.shape == pe.shape == pg.shape == po.shape) or pb.ndim != 1:
+            raise ValueError("plan arrays differ in length")
+        i64 = C.POINTER(C.c_int64)
+        v = C.c_float()
+        self._check(self.lib.zasr_audio_apply_gain(
+            self.handle, C.c_void_p(d_wav), int(n), pb.ctypes.data_as(i64),
+            pe.ctypes.data_as(i64), pg.ctypes.data_as(C_FP), po.ctypes.data_as(i64), pb.size,
+            rv.ctypes.data_as(C_FP), rv.size, C.byref(v), C.c_void_p(stream)))
+        return np.float32(v.value)

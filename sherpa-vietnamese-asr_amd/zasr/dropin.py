@@ -8,6 +8,9 @@
     # optional: Silero VAD on the GPU too (reads the reference's
     # models/silero-vad/silero_vad_16k_op15.onnx, or silero_config.json + silero_vad.safetensors)
     import core.vad_utils; install(core.asr_engine, vad_module=core.vad_utils)
+    # optional: preprocess_audio's level conditioning on the GPU (zasr.audio)
+    import core.audio_preprocessing
+    install(core.asr_engine, audio_module=core.audio_preprocessing)
 
 This build's modules live in the `zasr` package, so importing them never shadows the
 reference's `core` package (both trees can be on sys.path in any order).
@@ -35,6 +38,11 @@ What is rebound (the ASR hot path, core/asr_engine.py:698-1326):
                   get_cached_vad_probs, _run_vad_inference, get_vad_segments; and the
                   get_vad_segments / unload_vad_model names asr_engine imported from it
                   (core/asr_engine.py:580)
+  audio_preprocessing  (only when audio_module is given) compute_segment_rms,
+                  per_segment_rms_normalize, adaptive_peak_limit, preprocess_audio
+                  (core/asr_engine.py:2101 imports preprocess_audio from the module at call
+                  time, so the rebound name is the one it gets); apply_wpe_dereverberation
+                  stays the reference's
 
 get_ort, TranscriberPipeline, the overlap merge, ROVER vote and UI glue stay the
 reference's.  create_recognizer reads the hotword file and score through the reference
@@ -57,6 +65,8 @@ CALIBRATION_NAMES = ("detect_calibration_status", "run_device_calibration")
 VAD_NAMES = ("_get_vad_session", "unload_vad_model", "get_cached_vad_probs",
              "_run_vad_inference", "get_vad_segments")
 VAD_ENGINE_NAMES = ("get_vad_segments", "unload_vad_model")
+AUDIO_NAMES = ("compute_segment_rms", "per_segment_rms_normalize", "adaptive_peak_limit",
+               "preprocess_audio")
 
 
 def _caller_uses_wpe(frame) -> bool:
@@ -71,7 +81,8 @@ def _caller_uses_wpe(frame) -> bool:
 
 def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None,
             calibration_module: Optional[ModuleType] = None,
-            vad_module: Optional[ModuleType] = None) -> List[str]:
+            vad_module: Optional[ModuleType] = None,
+            audio_module: Optional[ModuleType] = None) -> List[str]:
     from zasr import asr_engine as ours
     from zasr import calibration as ours_cal
     from zasr import hardware_accel as ours_hw
@@ -143,4 +154,11 @@ def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None
             if hasattr(engine_module, n):
                 setattr(engine_module, n, getattr(ours_vad, n))
                 done.append("asr_engine." + n)
+    if audio_module is not None:
+        from zasr import audio as ours_audio
+        if audio_module is ours_audio:
+            raise ValueError("install() needs the reference's core.audio_preprocessing module")
+        for n in AUDIO_NAMES:
+            setattr(audio_module, n, getattr(ours_audio, n))
+            done.append("audio_preprocessing." + n)
     return done

@@ -27,8 +27,10 @@ build's config.json + model.safetensors); `tokens` is the symbol table (sherpa-o
 SymbolTable: a leading U+2581 is shown as a space, so `text` is the concatenation of the
 token strings).  Hotword phrases are tokenized with the directory's bpe.model, as
 create_recognizer does (no bpe.model: no hotwords).  16 kHz input only (the reference
-resamples on load).  Precision: `precision=` or ZASR_PRECISION, default
-zasr.asr_engine.DEFAULT_PRECISION.
+resamples on load), unless the recognizer is made with `resample_input=True`: then
+accept_waveform(rate, x) resamples that call's samples to 16 kHz through the device audio front
+end (zasr.audio.to_16k; sherpa-onnx's one-shot, flushed resampling of each call).  Precision:
+`precision=` or ZASR_PRECISION, default zasr.asr_engine.DEFAULT_PRECISION.
 """
 from __future__ import annotations
 
@@ -84,6 +86,9 @@ class OfflineStream:
 
     def accept_waveform(self, sample_rate: int, waveform) -> None:
         a = np.ascontiguousarray(np.asarray(waveform, dtype=np.float32).reshape(-1))
+        if int(sample_rate) != 16000 and self._rec._resample_input:
+            from zasr.audio import to_16k
+            a, sample_rate = np.ascontiguousarray(to_16k(a, int(sample_rate))), 16000
         fp = C.POINTER(C.c_float)
         self._rec._check(self._lib.zasr_stream_accept_waveform(
             self._h, int(sample_rate), a.ctypes.data_as(fp), int(a.shape[0])))
@@ -133,7 +138,7 @@ class OfflineRecognizer:
     def __init__(self, model_dir: str, tokens: str, decoding_method: str = "greedy_search",
                  max_active_paths: int = 4, hotwords_file: str = "",
                  hotwords_score: float = 1.5, precision: Optional[str] = None,
-                 device_id: Optional[int] = None):
+                 device_id: Optional[int] = None, resample_input: bool = False):
         from zasr import asr_engine as ae
         if decoding_method not in ("greedy_search", "modified_beam_search"):
             raise ValueError(f"decoding_method must be greedy_search or modified_beam_search, "
@@ -152,6 +157,7 @@ class OfflineRecognizer:
                                                       os.path.abspath(tokens).encode()))
         self._syms = _load_symbols(tokens)
         self._can_fall_back = prec == "f16x3"
+        self._resample_input = bool(resample_input)
         self._fallback: Optional["OfflineRecognizer"] = None
         self._ctor = (model_dir, tokens, decoding_method, int(max_active_paths), hotwords_file,
                       float(hotwords_score), dev)
@@ -166,11 +172,13 @@ class OfflineRecognizer:
                         hotwords_file: str = "", hotwords_score: float = 1.5,
                         blank_penalty: float = 0.0, provider: str = "cpu",
                         precision: Optional[str] = None, device_id: Optional[int] = None,
-                        **unused) -> "OfflineRecognizer":
+                        resample_input: bool = False, **unused) -> "OfflineRecognizer":
         """sherpa_onnx.OfflineRecognizer.from_transducer (streaming_asr.py:224-243).
         num_threads / provider / dither and the other CPU knobs do not apply to the GPU
         engine; sample_rate 16000, feature_dim 80 and blank_penalty 0 are the only values
-        the engine implements (the reference passes exactly these)."""
+        the engine implements (the reference passes exactly these): sample_rate is the
+        model's rate.  resample_input=True lets streams accept waveforms at other rates
+        (module docstring); the default refuses them."""
         if int(sample_rate) != 16000 or int(feature_dim) != 80:
             raise ValueError("the MI355X engine decodes 16 kHz audio into 80-bin fbank features")
         if float(blank_penalty) != 0.0:
@@ -182,7 +190,7 @@ class OfflineRecognizer:
             if not os.path.exists(p):
                 raise FileNotFoundError(f"model file not found: {p}")
         return cls(dirs.pop(), tokens, decoding_method, max_active_paths, hotwords_file,
-                   hotwords_score, precision, device_id)
+                   hotwords_score, precision, device_id, resample_input)
 
     def _check(self, rc):
         if rc != 0:

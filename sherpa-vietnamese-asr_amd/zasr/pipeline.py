@@ -150,10 +150,30 @@ class FullPipe:
         out = self.punct.restore(text, pause_hints=hints)
         return out, self.punct.runs - r0, self.punct.rows_run[n0:]
 
-    def prepare(self, audio: np.ndarray) -> None:
+    def prepare(self, audio: np.ndarray, sample_rate: int = 16000, vad_segments=None,
+                rms_normalize: bool = False, condition: bool = False) -> None:
+        """audio: the 16 kHz mono float32 signal (the defaults), or raw PCM for the device
+        audio front end (zasr.audio): [n] or [n, C], float32 or int16, at sample_rate.  Then
+        the signal in HBM is made by the front end, with the reference's quiet-file boost
+        and preprocess_audio(vad_segments, enable_rms_normalize=rms_normalize) applied when
+        `condition` is set, and copied back once for the chunk planner (host logic)."""
         import torch
         from zasr.plan import plan_chunks
-        a = np.ascontiguousarray(audio, np.float32)
+        raw = np.asarray(audio)
+        front = (int(sample_rate) != 16000 or condition or raw.ndim != 1
+                 or raw.dtype == np.int16)
+        d_front = None
+        if front:
+            from zasr import audio as fe
+            if raw.dtype != np.int16:
+                raw = raw.astype(np.float32, copy=False)
+            d_front = fe.to_16k(raw, int(sample_rate), device_out=True)
+            if condition:
+                fe.condition_device(d_front.data_ptr(), d_front.numel(), vad_segments or (),
+                                    16000, boost=True, enable_rms_normalize=rms_normalize)
+            a = d_front.cpu().numpy()
+        else:
+            a = np.ascontiguousarray(audio, np.float32)
         self.n = a.shape[0]
         plan = plan_chunks(a)                      # decode chunks, 3 s overlap
         regions = plan_chunks(a, overlap_sec=0.0)  # diarization speech regions
@@ -177,7 +197,7 @@ class FullPipe:
         self.r_len = [self.r_len_all[i] for i in self.mine_r]
         # window count bound: (frames - 150) / 60 + 2 per region
         self.cap = max(1, sum(max(1, (n // 160) // 60 + 2) for n in self.r_len))
-        self.d_audio = torch.from_numpy(a).cuda()
+        self.d_audio = d_front if front else torch.from_numpy(a).cuda()
         self.d_feats = torch.empty((self.cap, 150, 80), dtype=torch.float32, device="cuda")
         self.d_emb = torch.empty((self.cap, self.emb.dim), dtype=torch.float32, device="cuda")
         self.s_campp = torch.cuda.Stream()
