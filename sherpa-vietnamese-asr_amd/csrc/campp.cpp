@@ -7,7 +7,8 @@
 #include <cstring>
 
 #include "common.h"
-#include "gemm.h"
+#include "dense_gemm.h"
+#include "engine.h"
 #include "host_io.h"
 #include "onnx_io.h"
 
@@ -46,21 +47,6 @@ std::vector<int> ints(const Json& j, const char* k, std::vector<int> dflt) {
 }
 }  // namespace
 
-template <class T>
-T* CamppEngine::ws(const std::string& name, size_t count) {
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-  auto& e = ws_[name];
-  if (e.second < bytes) {
-    if (e.first) {
-      ZASR_HIP_CHECK(hipStreamSynchronize(st_));
-      ZASR_HIP_CHECK(hipFree(e.first));
-    }
-    ZASR_HIP_CHECK(hipMalloc(&e.first, bytes + bytes / 8));
-    e.second = bytes + bytes / 8;
-  }
-  return reinterpret_cast<T*>(e.first);
-}
-
 CamppEngine::CamppEngine(const std::string& dir, int device) : device_(device) {
   // campp_config.json + campp.safetensors, or the reference's campplus_cn_en_common_200k.onnx
   SafeTensors W;
@@ -81,14 +67,8 @@ CamppEngine::CamppEngine(const std::string& dir, int device) : device_(device) {
   ZASR_HIP_CHECK(hipSetDevice(device_));
   ZASR_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   st_ = stream_;
-  auto dev = [&](const float* src, size_t n) {
-    float* p = nullptr;
-    ZASR_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)));
-    ZASR_HIP_CHECK(hipMemcpy(p, src, n * sizeof(float), hipMemcpyHostToDevice));
-    allocs_.push_back(p);
-    return p;
-  };
-  auto devv = [&](const std::vector<float>& v) { return dev(v.data(), v.size()); };
+  auto dev = [&](const float* src, size_t n) { return store_.upload(src, n); };
+  auto devv = [&](const std::vector<float>& v) { return store_.upload(v); };
   auto conv2 = [&](const std::string& w, const std::string& bn, int ci, int ks) {
     Conv2 c;
     const HostTensor& t = W.get(w);
@@ -201,36 +181,25 @@ CamppEngine::CamppEngine(const std::string& dir, int device) : device_(device) {
       tw[2 * i] = std::cos(a);
       tw[2 * i + 1] = std::sin(a);
     }
-    ZASR_HIP_CHECK(hipMalloc(&d_twiddle_, 512 * sizeof(double)));
-    ZASR_HIP_CHECK(hipMemcpy(d_twiddle_, tw.data(), 512 * sizeof(double), hipMemcpyHostToDevice));
+    d_twiddle_ = store_.upload(tw);
     std::vector<float> win(400);
     for (int i = 0; i < 400; ++i) win[i] = (float)std::pow(0.5 - 0.5 * std::cos(2.0 * M_PI * i / 399.0), 0.85);
     d_window_ = dev(win.data(), 400);
     auto mel = [](double f) { return 1127.0 * std::log(1.0 + f / 700.0); };
     const double mlo = mel(20.0), mhi = mel(8000.0), delta = (mhi - mlo) / 81.0;
-    std::vector<int> meta(240);
-    std::vector<float> wts;
+    std::vector<float> banks(80 * 256, 0.f), wts;
     for (int b = 0; b < 80; ++b) {
       const double l = mlo + b * delta, ce = mlo + (b + 1) * delta, r = mlo + (b + 2) * delta;
-      int st = -1, en = -1;
-      std::vector<float> row(256, 0.f);
       for (int i = 0; i < 256; ++i) {
         const double m = mel(31.25 * i);
-        if (m > l && m < r) {
-          row[i] = (float)(m <= ce ? (m - l) / (ce - l) : (r - m) / (r - ce));
-          if (st < 0) st = i;
-          en = i;
-        }
+        if (m > l && m < r)
+          banks[b * 256 + i] = (float)(m <= ce ? (m - l) / (ce - l) : (r - m) / (r - ce));
       }
-      if (st < 0) st = en = 0;
-      meta[b] = st;
-      meta[80 + b] = en - st + 1;
-      meta[160 + b] = (int)wts.size();
-      for (int i = st; i <= en; ++i) wts.push_back(row[i]);
     }
-    ZASR_HIP_CHECK(hipMalloc(&d_mel_meta_, 240 * sizeof(int)));
-    ZASR_HIP_CHECK(hipMemcpy(d_mel_meta_, meta.data(), 240 * sizeof(int), hipMemcpyHostToDevice));
-    d_mel_w_ = dev(wts.data(), wts.size());
+    std::vector<int> meta;
+    pack_mel_banks(banks.data(), 256, meta, wts);
+    d_mel_meta_ = store_.upload(meta);
+    d_mel_w_ = devv(wts);
   }
   ZASR_HIP_CHECK(hipDeviceSynchronize());
 }
@@ -238,33 +207,15 @@ CamppEngine::CamppEngine(const std::string& dir, int device) : device_(device) {
 CamppEngine::~CamppEngine() {
   (void)hipSetDevice(device_);
   (void)hipStreamSynchronize(stream_);
-  for (void* p : allocs_) (void)hipFree(p);
-  for (auto& kv : ws_)
-    if (kv.second.first) (void)hipFree(kv.second.first);
-  if (d_twiddle_) (void)hipFree(d_twiddle_);
-  if (d_mel_meta_) (void)hipFree(d_mel_meta_);
-  (void)hipStreamDestroy(stream_);
+  (void)hipStreamDestroy(stream_);  // (store_ and ws_ free their buffers after this body)
 }
 
 void CamppEngine::gemm(const Lin& l, const float* A, int lda, int M, float* C, int ldc, int epi,
                        const float* aux, int ldaux, int aload, const float* a_scale,
                        const float* a_shift, const GemmIm2col1d* i2c) {
-  GemmParams p{};
-  p.A = A;
-  p.lda = lda;
-  p.B = l.w;
-  p.sbk = 1;
-  p.sbn = l.K;
-  p.C = C;
-  p.ldc = ldc;
-  p.bias = l.b;
+  GemmParams p = dense_gemm_params(l.w, l.b, l.N, l.K, A, lda, M, C, ldc);
   p.aux = aux;
   p.ldaux = ldaux;
-  p.M = M;
-  p.N = l.N;
-  p.K = l.K;
-  p.alpha = 1.f;
-  p.max_M = M;
   p.a_scale = a_scale;
   p.a_shift = a_shift;
   if (i2c) p.i2c = *i2c;

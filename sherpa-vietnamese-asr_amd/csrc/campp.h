@@ -7,11 +7,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -74,7 +74,9 @@ class CamppEngine {
     Lin transit;
   };
   template <class T>
-  T* ws(const std::string& name, size_t count);
+  T* ws(const std::string& name, size_t count) {
+    return ws_.get<T>(name, count, &st_);
+  }
   void gemm(const Lin& l, const float* A, int lda, int M, float* C, int ldc, int epi,
             const float* aux = nullptr, int ldaux = 0, int aload = 0,
             const float* a_scale = nullptr, const float* a_shift = nullptr,
@@ -95,8 +97,8 @@ class CamppEngine {
   std::vector<Block> blocks_;
   float *out_s_ = nullptr, *out_b_ = nullptr;
   Lin dense_;
-  std::vector<void*> allocs_;
-  std::map<std::string, std::pair<void*, size_t>> ws_;
+  DeviceStore store_;  // weights and tables
+  Workspace ws_;
   // fbank tables
   double* d_twiddle_ = nullptr;
   float* d_window_ = nullptr;

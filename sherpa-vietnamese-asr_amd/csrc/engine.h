@@ -1,5 +1,6 @@
 // Host runtime of libzasr: device-resident model, per-batch workspace, and the encoder /
-// search drivers that sequence the HIP kernels on one stream.
+// search drivers that sequence the HIP kernels on one stream (engine.cpp, engine_load.cpp,
+// engine_encoder.cpp, engine_search.cpp, hotword_dfa.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,10 +9,13 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "gemm.h"
 #include "kernels.h"
 
 namespace zasr {
+
+class SafeTensors;
 
 struct ModelConfig {
   std::string name;
@@ -23,6 +27,31 @@ struct ModelConfig {
     int m = 0;
     for (int d : dims) m = d > m ? d : m;
     return m;
+  }
+};
+
+// the values of ZASR_PRECISION_* (zasr.h)
+enum class Precision : int { Fp32 = 0, Bf16 = 1, Bf16Enc = 2, Bf16x3 = 3, Bf16x6 = 4, F16x3 = 5 };
+
+// what the drivers ask about the precision mode, decided once at construction
+struct PrecisionFacts {
+  Precision mode = Precision::Fp32;
+  bool bf16_act = false;  // bf16 weights and GEMM -> GEMM activations (Bf16, Bf16Enc)
+  // the `pieces` code of the split modes: 2 / 3 bf16 pieces (bf16x3 / bf16x6), kPiecesF16 for
+  // the two fp16 pieces of f16x3 (gemm.h); 0 otherwise
+  int pieces = 0;
+  bool f16x3 = false;
+  bool flash = false;         // the flash attention kernels (every mode but fp32)
+  bool nonlin_fused = false;  // NonlinAttention inside the flash kernel (bf16 modes, f16x3)
+  bool f32_search = false;    // bf16 encoder with the joiner and the search in f32 (Bf16Enc)
+  PrecisionFacts() = default;
+  explicit PrecisionFacts(Precision m) : mode(m) {
+    bf16_act = m == Precision::Bf16 || m == Precision::Bf16Enc;
+    f16x3 = m == Precision::F16x3;
+    pieces = m == Precision::Bf16x3 ? 2 : m == Precision::Bf16x6 ? 3 : f16x3 ? kPiecesF16 : 0;
+    flash = bf16_act || pieces > 0;
+    nonlin_fused = bf16_act || f16x3;
+    f32_search = m == Precision::Bf16Enc;
   }
 };
 
@@ -38,6 +67,9 @@ struct DLin {
   // split modes, the conv modules' in_proj: rows (and bias) interleaved so output columns
   // 2c / 2c + 1 are the GLU halves of channel c -- the GEMM epilogue applies the GLU (EPI_GLU)
   bool glu = false;
+  // the host images of w and b while the model loads (the packers read them); null afterwards
+  const float* hw = nullptr;
+  const float* hb = nullptr;
 };
 
 struct DLayer {
@@ -77,7 +109,6 @@ struct DModel {
   float* dec_tap0 = nullptr;  // [V][D] conv tap 0 of each embedding row
   float* dec_tap1 = nullptr;  // [V][D] conv tap 1
   int pmax = 0;
-  std::vector<void*> allocations;
 };
 
 struct HotwordDFA {
@@ -87,6 +118,11 @@ struct HotwordDFA {
 };
 HotwordDFA build_hotword_dfa(const std::vector<std::vector<int>>& phrases,
                              const std::vector<float>& scores, int V);
+
+// 80 dense filter rows over the FFT's power bins (row stride n_bins, bins 0 .. 255 read) as the
+// fbank kernel's tables: meta = start[80], len[80], woff[80]; wts = the nonzero runs
+void pack_mel_banks(const float* banks, int n_bins, std::vector<int>& meta,
+                    std::vector<float>& wts);
 
 struct TokenResult {
   std::vector<int> tok, frame;
@@ -159,13 +195,38 @@ class Engine {
   std::mutex mu;
 
  private:
-  struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-  };
+  // named grow-only workspace buffer (device_mem.h); the buffers are in use on several
+  // streams, so growth drains the whole device
   template <class T>
-  T* ws(const std::string& name, size_t count);
+  T* ws(const std::string& name, size_t count) {
+    return ws_tag_.empty() ? ws_.get<T>(name, count, nullptr)
+                           : ws_.get<T>(ws_tag_ + name, count, nullptr);
+  }
   void upload(void* dst, const void* src, size_t bytes);
+  // host blocks (row_len[i] rows of `width` floats at rows[i]; those under min_len rows
+  // skipped) packed back to back into workspace buffer `name` on st_
+  float* upload_rows(const char* name, const std::vector<const float*>& rows,
+                     const std::vector<long>& row_len, int width, long min_len);
+
+  // ---- model load (engine_load.cpp) ----
+  void load_model(const SafeTensors& W);
+  void load_frontend(const SafeTensors& W);
+  void load_stacks(const SafeTensors& W, std::vector<std::vector<float>>& host_images);
+  void load_decoder(const SafeTensors& W);
+  void load_split_operands();  // bf16x3 / bf16x6 / f16x3
+  void load_bf16_operands();   // bf16 modes
+  void build_dec_table();
+  void load_fbank_tables();
+  void load_hotword_tables();
+  DLin load_linear(const SafeTensors& W, const std::string& prefix, int N, int K);
+  // an MFMA-fragment-order weight image built on the host by `pack` into `elems` bf16-sized
+  // elements, uploaded
+  template <class Pack>
+  void* upload_packed(size_t elems, Pack pack) {
+    std::vector<__bf16> pk(elems);
+    pack(pk.data());
+    return store_.upload(pk);
+  }
 
   // a batch whose encoder output is enqueued (enc_out slot `slot`), waiting for its search
   struct Pending {
@@ -223,14 +284,48 @@ class Engine {
     size_t cap = 0;
   };
   ResPin res_pin_[kMaxJobs];
+
+  // ---- encoder driver (engine_encoder.cpp) ----
+  // what every layer of one stack shares, built once per stack in run_encoder
+  struct StackCtx {
+    const DStack* stk = nullptr;
+    int R = 0;                         // packed rows at the stack's rate
+    int B = 0;                         // sequences
+    const int* off = nullptr;          // [B + 1] row offsets (device)
+    const int* map = nullptr;          // row -> sequence (device)
+    const long* a_off = nullptr;       // [B] head 0's weight block of each sequence
+    const GemmSlice* nl_slices = nullptr;  // NonlinAttention's per-sequence GEMM slices
+    int maxL = 0;
+    const int* o8 = nullptr;           // [B + 1] 32-padded column offsets of t1^T
+    int R8 = 0;                        // their total
+    AttnBlockMaps bm{};
+  };
+  // the attention weights of one layer, shared by nonlin_attention, self_attn1 and self_attn2
+  struct LayerAttn {
+    float* qkp = nullptr;    // fp32: q / k / p projections
+    float* A = nullptr;      // head 0's normalised weights (fp32, bf16x3, bf16x6)
+    float* stats = nullptr;
+    AttnFlashArgs fa{};      // flash modes
+  };
   // X: the layer's input; Xalt: a second buffer of its size.  Returns the one that holds the
   // output: Xalt when feed_forward1 ran out of place (ff1_fused; X then stays as the input),
   // else X.  orig_ready: the previous layer wrote this layer's copy of its input (ly_orig);
   // copy_for_next: write the next layer's.
-  float* layer_forward(const DStack& stk, const DLayer& ly, float* X, float* Xalt, int R,
-                       const int* d_off, const int* d_map, const std::vector<int>& lens,
-                       const long* d_aoff, const void* d_slices_nl, int maxL, const int* d_o8,
-                       int R8, const AttnBlockMaps& bm, bool orig_ready, bool copy_for_next);
+  float* layer_forward(const StackCtx& c, const DLayer& ly, float* X, float* Xalt, bool orig_ready,
+                       bool copy_for_next);
+  LayerAttn attention_weights(const StackCtx& c, const DLayer& ly, const float* X);
+  // O: the layer's input (bypass_mid in feed_forward2's epilogue); src: out of place (fused
+  // routes only)
+  void feed_forward(const StackCtx& c, const DLayer& ly, int k, float* X, const float* O,
+                    const float* src = nullptr);
+  void nonlin_attention(const StackCtx& c, const DLayer& ly, float* X, const LayerAttn& at);
+  void self_attention(const StackCtx& c, const DLayer& ly, int k, float* X, const LayerAttn& at);
+  void conv_module(const StackCtx& c, const DLayer& ly, int k, float* X);
+  // head 0's fused NonlinAttention pass of the flash kernel (mode 3)
+  void launch_nonlin_flash(const StackCtx& c, const LayerAttn& at, const void* t1t, int hid,
+                           const void* y, void* z);
+  // a Conv2dSubsampling conv as an implicit-im2col GEMM (p: A, C, slices and sizes set)
+  void frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_bf16, bool c_bf16);
   bool ff1_fused(const DStack& stk, const DLayer& ly) const;
   // byp_orig / byp_scale (split modes, EPI_RESADD): bypass_mid in the epilogue
   void linear(const DLin& l, const float* A, int lda, int M, float* C, int ldc, int epi,
@@ -241,6 +336,10 @@ class Engine {
   void linear_h(const DLin& l, const void* A, bool a_bf16, int lda, int M, void* C, bool c_bf16,
                 int ldc, int epi, const float* byp_orig = nullptr,
                 const float* byp_scale = nullptr);
+  // a layer projection whose intermediate side is bf16 in the bf16 modes (a16 / c16 say which
+  // side that is) and f32 otherwise: linear_h or linear
+  void project(const DLin& l, const void* A, bool a16, int lda, int M, void* C, bool c16, int ldc,
+               int epi);
   void ensure_pos_tables(int max_len);
 
   // timing
@@ -272,13 +371,7 @@ class Engine {
   [[maybe_unused]] bool greedy_ = false;
   // make main_st wait for every encoder stream of a batch pipeline that is not main_st
   void order_after_encoders(const hipStream_t* enc_st, int E, hipStream_t main_st);
-  int precision_ = 0;
-  // bf16 pieces per operand of the split-bf16 modes (bf16x3: 2, bf16x6: 3), 0 otherwise
-  // the `pieces` code of the split modes: 2 / 3 bf16 pieces (bf16x3 / bf16x6), kPiecesF16
-  // for the two fp16 pieces of f16x3 (gemm.h); 0 otherwise
-  int split_pieces() const {
-    return precision_ == 3 ? 2 : precision_ == 4 ? 3 : precision_ == 5 ? kPiecesF16 : 0;
-  }
+  PrecisionFacts prec_;
   hipStream_t stream_ = nullptr;
   hipStream_t stream2_ = nullptr;  // searches (high priority: overlaps the next batch's encoder)
   hipStream_t stream3_ = nullptr;  // the second group of a beam search (high priority)
@@ -294,7 +387,8 @@ class Engine {
   const float* host_wav_ = nullptr;
   hipStream_t copy_st_ = nullptr;
   hipEvent_t upload_ev_[kMaxEnc + 1] = {};
-  std::map<std::string, Buf> ws_;
+  DeviceStore store_;  // weights and tables
+  Workspace ws_;
   // fbank tables
   double* d_twiddle_ = nullptr;
   float* d_window_ = nullptr;

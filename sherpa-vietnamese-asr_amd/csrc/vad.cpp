@@ -7,7 +7,7 @@
 #include <cstring>
 
 #include "common.h"
-#include "gemm.h"
+#include "dense_gemm.h"
 #include "host_io.h"
 #include "onnx_io.h"
 #include "kernels.h"
@@ -16,21 +16,6 @@ namespace zasr {
 
 namespace {
 constexpr int VW = 512, VIN = 576, VFR = 4, VFL = 256, VH = 128;
-}
-
-template <class T>
-T* VadEngine::ws(const std::string& name, size_t count) {
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-  auto& e = ws_[name];
-  if (e.second < bytes) {
-    if (e.first) {
-      ZASR_HIP_CHECK(hipStreamSynchronize(st_));
-      ZASR_HIP_CHECK(hipFree(e.first));
-    }
-    ZASR_HIP_CHECK(hipMalloc(&e.first, bytes + bytes / 8));
-    e.second = bytes + bytes / 8;
-  }
-  return reinterpret_cast<T*>(e.first);
 }
 
 VadEngine::VadEngine(const std::string& dir, int device) : device_(device) {
@@ -52,13 +37,7 @@ VadEngine::VadEngine(const std::string& dir, int device) : device_(device) {
     const char* e = std::getenv("ZASR_VAD_PIT");
     pit_ = !(e && e[0] == '0');
   }
-  auto dev = [&](const float* src, size_t n) {
-    float* p = nullptr;
-    ZASR_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)));
-    ZASR_HIP_CHECK(hipMemcpy(p, src, n * sizeof(float), hipMemcpyHostToDevice));
-    allocs_.push_back(p);
-    return p;
-  };
+  auto dev = [&](const float* src, size_t n) { return store_.upload(src, n); };
   auto get = [&](const std::string& n, size_t numel) {
     const HostTensor& t = W.get("_model." + n);
     ZASR_REQUIRE(t.numel == numel, "Silero VAD: bad size of " + n);
@@ -108,28 +87,12 @@ VadEngine::VadEngine(const std::string& dir, int device) : device_(device) {
 VadEngine::~VadEngine() {
   (void)hipSetDevice(device_);
   (void)hipStreamSynchronize(st_);
-  for (void* p : allocs_) (void)hipFree(p);
-  for (auto& kv : ws_)
-    if (kv.second.first) (void)hipFree(kv.second.first);
-  (void)hipStreamDestroy(st_);
+  (void)hipStreamDestroy(st_);  // (store_ and ws_ free their buffers after this body)
 }
 
 void VadEngine::gemm(const Lin& l, const float* A, long M, float* C, int ldc, int epi) {
   ZASR_REQUIRE(M < (1L << 31), "Silero VAD: too many windows in one call");
-  GemmParams p{};
-  p.A = A;
-  p.lda = l.K;
-  p.B = l.w;
-  p.sbk = 1;
-  p.sbn = l.K;
-  p.C = C;
-  p.ldc = ldc;
-  p.bias = l.b;
-  p.M = (int)M;
-  p.N = l.N;
-  p.K = l.K;
-  p.alpha = 1.f;
-  p.max_M = (int)M;
+  const GemmParams p = dense_gemm_params(l.w, l.b, l.N, l.K, A, l.K, (int)M, C, ldc);
   gemm_f32(p, epi, ALOAD_DENSE, false, st_);
 }
 

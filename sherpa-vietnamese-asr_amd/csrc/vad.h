@@ -7,10 +7,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
+
+#include "device_mem.h"
 
 namespace zasr {
 
@@ -41,7 +42,9 @@ class VadEngine {
     int N = 0, K = 0;
   };
   template <class T>
-  T* ws(const std::string& name, size_t count);
+  T* ws(const std::string& name, size_t count) {
+    return ws_.get<T>(name, count, &st_);
+  }
   void gemm(const Lin& l, const float* A, long M, float* C, int ldc, int epi);
   // encoder + LSTM input projection for n windows whose frames are in ws "frames" -> ws "gx"
   float* encode(long n);
@@ -58,8 +61,8 @@ class VadEngine {
   Lin ih_;
   float *whh_ = nullptr, *bhh_ = nullptr, *wd_ = nullptr;
   float bd_ = 0.f;
-  std::vector<void*> allocs_;
-  std::map<std::string, std::pair<void*, size_t>> ws_;
+  DeviceStore store_;  // weights
+  Workspace ws_;
 };
 
 }  // namespace zasr

@@ -6,27 +6,12 @@
 #include <cstring>
 
 #include "common.h"
-#include "gemm.h"
+#include "dense_gemm.h"
 #include "host_io.h"
 #include "onnx_io.h"
 #include "kernels.h"
 
 namespace zasr {
-
-template <class T>
-T* VibertEngine::ws(const std::string& name, size_t count) {
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-  auto& e = ws_[name];
-  if (e.second < bytes) {
-    if (e.first) {
-      ZASR_HIP_CHECK(hipStreamSynchronize(st_));
-      ZASR_HIP_CHECK(hipFree(e.first));
-    }
-    ZASR_HIP_CHECK(hipMalloc(&e.first, bytes + bytes / 8));
-    e.second = bytes + bytes / 8;
-  }
-  return reinterpret_cast<T*>(e.first);
-}
 
 VibertEngine::VibertEngine(const std::string& dir, int device) : device_(device) {
   // vibert_config.json + vibert.safetensors, or the reference's vibert-capu.onnx (onnx_io.h)
@@ -46,13 +31,7 @@ VibertEngine::VibertEngine(const std::string& dir, int device) : device_(device)
   ZASR_REQUIRE(hd == 16 || hd == 32 || hd == 64, "ViBERT: head dim 16, 32 or 64");
   ZASR_HIP_CHECK(hipSetDevice(device_));
   ZASR_HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  auto dev = [&](const float* src, size_t n) {
-    float* p = nullptr;
-    ZASR_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)));
-    ZASR_HIP_CHECK(hipMemcpy(p, src, n * sizeof(float), hipMemcpyHostToDevice));
-    allocs_.push_back(p);
-    return p;
-  };
+  auto dev = [&](const float* src, size_t n) { return store_.upload(src, n); };
   auto get = [&](const std::string& n, size_t numel) {
     const HostTensor& t = W.get(n);
     ZASR_REQUIRE(t.numel == numel, "ViBERT: bad size of " + n);
@@ -108,27 +87,11 @@ VibertEngine::VibertEngine(const std::string& dir, int device) : device_(device)
 VibertEngine::~VibertEngine() {
   (void)hipSetDevice(device_);
   (void)hipStreamSynchronize(st_);
-  for (void* p : allocs_) (void)hipFree(p);
-  for (auto& kv : ws_)
-    if (kv.second.first) (void)hipFree(kv.second.first);
-  (void)hipStreamDestroy(st_);
+  (void)hipStreamDestroy(st_);  // (store_ and ws_ free their buffers after this body)
 }
 
 void VibertEngine::gemm(const Lin& l, const float* A, int M, float* C, int epi) {
-  GemmParams p{};
-  p.A = A;
-  p.lda = l.K;
-  p.B = l.w;
-  p.sbk = 1;
-  p.sbn = l.K;
-  p.C = C;
-  p.ldc = l.N;
-  p.bias = l.b;
-  p.M = M;
-  p.N = l.N;
-  p.K = l.K;
-  p.alpha = 1.f;
-  p.max_M = M;
+  const GemmParams p = dense_gemm_params(l.w, l.b, l.N, l.K, A, l.K, M, C, l.N);
   gemm_f32(p, epi, ALOAD_DENSE, false, st_);
 }
 
@@ -162,20 +125,10 @@ void VibertEngine::run_host(const long* ids, const long* am, const long* tt, con
     gemm(ly.qkv, X, (int)R, QKV, EPI_NONE);
     VibertAttnArgs a{QKV, d_in + R, CTX, L, H_, 1.f / std::sqrt((float)(H_ / heads_))};
     launch_vibert_attention(a, B, heads_, st_);
-    {
-      GemmParams p{};
-      p.A = CTX; p.lda = H_; p.B = ly.ao.w; p.sbk = 1; p.sbn = H_; p.C = X; p.ldc = H_;
-      p.bias = ly.ao.b; p.M = (int)R; p.N = H_; p.K = H_; p.alpha = 1.f; p.max_M = (int)R;
-      gemm_f32(p, EPI_RESADD, ALOAD_DENSE, false, st_);
-    }
+    gemm(ly.ao, CTX, (int)R, X, EPI_RESADD);  // [H_][H_]
     launch_vibert_layernorm(X, R, H_, ly.ln1_g, ly.ln1_b, eps_, st_);
     gemm(ly.inter, X, (int)R, INT, EPI_GELU);
-    {
-      GemmParams p{};
-      p.A = INT; p.lda = inter_; p.B = ly.out.w; p.sbk = 1; p.sbn = inter_; p.C = X; p.ldc = H_;
-      p.bias = ly.out.b; p.M = (int)R; p.N = H_; p.K = inter_; p.alpha = 1.f; p.max_M = (int)R;
-      gemm_f32(p, EPI_RESADD, ALOAD_DENSE, false, st_);
-    }
+    gemm(ly.out, INT, (int)R, X, EPI_RESADD);  // [H_][inter_]
     launch_vibert_layernorm(X, R, H_, ly.ln2_g, ly.ln2_b, eps_, st_);
   }
   const int BW = B * W;

@@ -6,10 +6,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
+
+#include "device_mem.h"
 
 namespace zasr {
 
@@ -36,7 +37,9 @@ class VibertEngine {
     float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
   };
   template <class T>
-  T* ws(const std::string& name, size_t count);
+  T* ws(const std::string& name, size_t count) {
+    return ws_.get<T>(name, count, &st_);
+  }
   void gemm(const Lin& l, const float* A, int M, float* C, int epi);
 
   int device_ = 0, H_ = 0, heads_ = 0, inter_ = 0, labels_ = 0, detect_ = 0, max_pos_ = 0;
@@ -46,8 +49,8 @@ class VibertEngine {
   float *word_ = nullptr, *pos_ = nullptr, *type_ = nullptr, *eln_g_ = nullptr, *eln_b_ = nullptr;
   std::vector<Layer> layers_;
   Lin heads_lin_;  // classifier rows then detector rows
-  std::vector<void*> allocs_;
-  std::map<std::string, std::pair<void*, size_t>> ws_;
+  DeviceStore store_;  // weights
+  Workspace ws_;
 };
 
 }  // namespace zasr

@@ -1,7 +1,7 @@
 """Drop-in `core/hotword_context.py` host side.
 
 The Aho-Corasick automaton itself (reference `core/hotword_context.py:17-184`) is built and
-flattened inside libzasr (`build_hotword_dfa`, csrc/engine.cpp) and walked on device by the
+flattened inside libzasr (`build_hotword_dfa`, csrc/hotword_dfa.cpp) and walked on device by the
 search kernel.  What stays on the host is what the reference also does on the host: parse
 the hotwords file (:191-222) and tokenize phrases with the model's sentencepiece model
 (:225-259).
