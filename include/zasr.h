@@ -457,6 +457,41 @@ int zasr_selftest_seam(int32_t nseq, const int32_t* L, int32_t d, int32_t ds, in
 int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
                                  int32_t order, uint32_t* out, int64_t cap, int32_t* grid);
 
+/* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
+   core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the
+   eigenvectors; the eigengap rule, k-means and the segment logic are host code in
+   zasr/diarize.py).  2 <= N <= 8192 windows, 1 <= D <= 512; anything else is
+   ZASR_ERR_INVALID.  Every entry selects the handle's device first; results are bit-identical
+   from run to run.  Stage entries take device pointers and are ordered on `stream`. */
+typedef struct zasr_diar zasr_diar;
+int zasr_diar_create(int32_t device_id, zasr_diar** out);
+void zasr_diar_destroy(zasr_diar* h);
+/* _cosine_similarity (:183-189): d_M [N][N] = Xn Xn^T with Xn = X / (|X|_2 + 1e-10), float32
+   throughout (D % 4 == 0, which includes CAM++'s 192, takes the exact-f32 MFMA GEMM). */
+int zasr_diar_similarity(zasr_diar* h, const float* d_X, int32_t N, int32_t D, float* d_M,
+                         void* stream);
+/* p_pruning, symmetrise and the degrees (:201-215), d_M in place: per row the
+   n_elems = max(min(int((1 - pval) N), N - min_pnum), 0) smallest entries become 0 (entries
+   equal to the threshold value survive from the lowest column index up; the reference's
+   argsort leaves ties undefined), M <- 0.5 (M + M^T), diagonal <- 0, d_deg[i] = sum_j |M_ij|
+   in float64.  0 <= pval <= 1, min_pnum >= 1. */
+int zasr_diar_prune(zasr_diar* h, float* d_M, int32_t N, double pval, int32_t min_pnum,
+                    double* d_deg, void* stream);
+/* numpy.linalg.eigh(L)'s k smallest eigenpairs (:215-218, L = diag(deg) - M, never stored):
+   lambdas [k] ascending and vecs [N][k] on the host, 1 <= k <= min(16, N), by
+   Chebyshev-filtered subspace iteration in float64 until every residual |L v - lambda v|_2 is
+   at most 1e-7 of the Gershgorin bound 2.02 max deg.  *passes (nullable) = outer passes run.
+   ZASR_ERR_RUNTIME with a message if 200 passes do not converge.  Synchronises `stream`. */
+int zasr_diar_eigs(zasr_diar* h, const float* d_M, const double* d_deg, int32_t N, int32_t k,
+                   double* lambdas, double* vecs, int32_t* passes, void* stream);
+/* the three stages on X [N][D] (host, or device when x_on_device) in the handle's workspace */
+int zasr_diar_spectral_embed(zasr_diar* h, const float* X, int32_t x_on_device, int32_t N,
+                             int32_t D, double pval, int32_t min_pnum, int32_t k,
+                             double* lambdas, double* vecs, void* stream);
+/* passes and block Laplacian products of the handle's last eigs / spectral_embed (no reference
+   counterpart: a diagnostic read by the tests and tools/diar_bench.py) */
+int zasr_diar_last_stats(zasr_diar* h, int32_t* passes, int64_t* applications);
+
 /* profiling: per-kernel-class HIP-event timing on the handle's stream.  on = 0 off,
    1 kernel classes, 2 kernel classes with the encoder GEMMs split by shape
    ("enc_gemm|M|K|N|w16|a16|c16|epi" class names, for the per-shape roofline table) */

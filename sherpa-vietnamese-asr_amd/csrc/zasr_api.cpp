@@ -12,6 +12,7 @@
 #include "audio.h"
 #include "campp.h"
 #include "common.h"
+#include "diar.h"
 #include "vad.h"
 #include "vibert.h"
 #include "engine.h"
@@ -61,6 +62,11 @@ struct zasr_vad {
 
 struct zasr_audio {
   std::unique_ptr<zasr::AudioFrontEnd> eng;
+};
+
+struct zasr_diar {
+  std::unique_ptr<zasr::DiarEngine> eng;
+  int last_passes = 0;
 };
 
 namespace {
@@ -898,6 +904,104 @@ int zasr_audio_apply_gain(zasr_audio* h, float* d_wav, int64_t n, const int64_t*
                                (long)n_ramp_values, reinterpret_cast<hipStream_t>(stream));
     return (int)ZASR_OK;
   });
+}
+
+// ---- speaker diarization: spectral embedding (diar.h) ----
+namespace {
+int diar_shape_error(int32_t N, int32_t D) {
+  if (N < zasr::kDiarMinN || N > zasr::kDiarMaxN)
+    return fail(ZASR_ERR_INVALID, "N must be in 2..8192 windows");
+  if (D < 1 || D > zasr::kDiarMaxD) return fail(ZASR_ERR_INVALID, "D must be in 1..512");
+  return ZASR_OK;
+}
+int diar_prune_error(double pval, int32_t min_pnum) {
+  if (!(pval >= 0.0 && pval <= 1.0)) return fail(ZASR_ERR_INVALID, "pval must be in [0, 1]");
+  if (min_pnum < 1) return fail(ZASR_ERR_INVALID, "min_pnum must be at least 1");
+  return ZASR_OK;
+}
+int diar_k_error(int32_t N, int32_t k) {
+  if (k < 1 || k > zasr::kDiarMaxK || k > N)
+    return fail(ZASR_ERR_INVALID, "k must be in 1..min(16, N)");
+  return ZASR_OK;
+}
+}  // namespace
+
+int zasr_diar_create(int32_t device_id, zasr_diar** out) {
+  if (!out) return fail(ZASR_ERR_INVALID, "null out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_diar;
+    try {
+      h->eng.reset(new zasr::DiarEngine(device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_diar_destroy(zasr_diar* h) { delete h; }
+
+int zasr_diar_similarity(zasr_diar* h, const float* d_X, int32_t N, int32_t D, float* d_M,
+                         void* stream) {
+  if (const int rc = diar_shape_error(N, D)) return rc;
+  if (!h || !d_X || !d_M) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->similarity(d_X, N, D, d_M, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_diar_prune(zasr_diar* h, float* d_M, int32_t N, double pval, int32_t min_pnum,
+                    double* d_deg, void* stream) {
+  if (const int rc = diar_shape_error(N, 1)) return rc;
+  if (const int rc = diar_prune_error(pval, min_pnum)) return rc;
+  if (!h || !d_M || !d_deg) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->prune(d_M, N, pval, min_pnum, d_deg, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_diar_eigs(zasr_diar* h, const float* d_M, const double* d_deg, int32_t N, int32_t k,
+                   double* lambdas, double* vecs, int32_t* passes, void* stream) {
+  if (const int rc = diar_shape_error(N, 1)) return rc;
+  if (const int rc = diar_k_error(N, k)) return rc;
+  if (!h || !d_M || !d_deg || !lambdas || !vecs) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->last_passes = h->eng->eigs(d_M, d_deg, N, k, lambdas, vecs,
+                                  reinterpret_cast<hipStream_t>(stream));
+    if (passes) *passes = h->last_passes;
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_diar_spectral_embed(zasr_diar* h, const float* X, int32_t x_on_device, int32_t N,
+                             int32_t D, double pval, int32_t min_pnum, int32_t k,
+                             double* lambdas, double* vecs, void* stream) {
+  if (const int rc = diar_shape_error(N, D)) return rc;
+  if (const int rc = diar_prune_error(pval, min_pnum)) return rc;
+  if (const int rc = diar_k_error(N, k)) return rc;
+  if (!h || !X || !lambdas || !vecs) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->last_passes = h->eng->spectral_embed(X, x_on_device != 0, N, D, pval, min_pnum, k, lambdas,
+                                            vecs, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_diar_last_stats(zasr_diar* h, int32_t* passes, int64_t* applications) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  if (passes) *passes = h->last_passes;
+  if (applications) *applications = h->eng->last_applications;
+  return ZASR_OK;
 }
 
 // ---- offline streams (sherpa-onnx OfflineStream surface) ----

@@ -41,6 +41,8 @@ EXPORTS = (
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
+    "zasr_diar_create", "zasr_diar_destroy", "zasr_diar_similarity", "zasr_diar_prune",
+    "zasr_diar_eigs", "zasr_diar_spectral_embed", "zasr_diar_last_stats",
 )
 
 
@@ -252,6 +254,21 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_audio_segment_sumsq.restype = C.c_int
     lib.zasr_audio_apply_gain.argtypes = [P, P, I64, i64p, i64p, fp, i64p, I32, fp, I64, fp, P]
     lib.zasr_audio_apply_gain.restype = C.c_int
+    dp, DBL = C.POINTER(C.c_double), C.c_double
+    lib.zasr_diar_create.argtypes = [I32, C.POINTER(P)]
+    lib.zasr_diar_create.restype = C.c_int
+    lib.zasr_diar_destroy.argtypes = [P]
+    lib.zasr_diar_destroy.restype = None
+    lib.zasr_diar_similarity.argtypes = [P, P, I32, I32, P, P]
+    lib.zasr_diar_similarity.restype = C.c_int
+    lib.zasr_diar_prune.argtypes = [P, P, I32, DBL, I32, P, P]
+    lib.zasr_diar_prune.restype = C.c_int
+    lib.zasr_diar_eigs.argtypes = [P, P, P, I32, I32, dp, dp, i32p, P]
+    lib.zasr_diar_eigs.restype = C.c_int
+    lib.zasr_diar_spectral_embed.argtypes = [P, P, I32, I32, I32, DBL, I32, I32, dp, dp, P]
+    lib.zasr_diar_spectral_embed.restype = C.c_int
+    lib.zasr_diar_last_stats.argtypes = [P, i32p, i64p]
+    lib.zasr_diar_last_stats.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -1042,3 +1059,81 @@ class AudioFrontEnd:
             pe.ctypes.data_as(i64), pg.ctypes.data_as(C_FP), po.ctypes.data_as(i64), pb.size,
             rv.ctypes.data_as(C_FP), rv.size, C.byref(v), C.c_void_p(stream)))
         return np.float32(v.value)
+
+
+class Diarizer:
+    """The device side of the diarization clustering (include/zasr.h zasr_diar_*): cosine
+    similarity, prune + symmetrise + degrees, and the smallest eigenpairs of the Laplacian.
+    Stage entries take device pointers (ints); spectral_embed takes a numpy array [N][D]
+    (host) or a device pointer with N and D.  zasr/diarize.py is the host logic over it."""
+
+    def __init__(self, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        if self.lib.zasr_diar_create(int(device_id), C.byref(h)) != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+        self.handle = h
+        self.device_id = int(device_id)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_diar_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def similarity(self, d_X: int, N: int, D: int, d_M: int, stream: int = 0) -> None:
+        self._check(self.lib.zasr_diar_similarity(self.handle, C.c_void_p(d_X), int(N), int(D),
+                                                  C.c_void_p(d_M), C.c_void_p(stream)))
+
+    def prune(self, d_M: int, N: int, pval: float, min_pnum: int, d_deg: int,
+              stream: int = 0) -> None:
+        self._check(self.lib.zasr_diar_prune(self.handle, C.c_void_p(d_M), int(N), float(pval),
+                                             int(min_pnum), C.c_void_p(d_deg), C.c_void_p(stream)))
+
+    def eigs(self, d_M: int, d_deg: int, N: int, k: int, stream: int = 0):
+        """(lambdas [k], vecs [N][k], outer passes)."""
+        dp = C.POINTER(C.c_double)
+        lam = np.zeros(max(int(k), 0), np.float64)
+        vec = np.zeros((max(int(N), 0), max(int(k), 0)), np.float64)
+        passes = C.c_int32()
+        self._check(self.lib.zasr_diar_eigs(self.handle, C.c_void_p(d_M), C.c_void_p(d_deg), int(N),
+                                            int(k), lam.ctypes.data_as(dp), vec.ctypes.data_as(dp),
+                                            C.byref(passes), C.c_void_p(stream)))
+        return lam, vec, int(passes.value)
+
+    def spectral_embed(self, X, pval: float = 0.02, min_pnum: int = 6, k: int = 16,
+                       N: Optional[int] = None, D: Optional[int] = None, stream: int = 0):
+        """(lambdas [k], vecs [N][k]) of the pruned cosine Laplacian of the rows of X."""
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2:
+                raise ValueError("X must be [N][D]")
+            keep = np.ascontiguousarray(X, np.float32)
+            N, D = keep.shape
+            ptr, on_device = keep.ctypes.data, 0
+        else:
+            if N is None or D is None:
+                raise ValueError("a device X needs N and D")
+            keep, ptr, on_device = None, int(X), 1
+        dp = C.POINTER(C.c_double)
+        lam = np.zeros(max(int(k), 0), np.float64)
+        vec = np.zeros((max(int(N), 0), max(int(k), 0)), np.float64)
+        self._check(self.lib.zasr_diar_spectral_embed(
+            self.handle, C.c_void_p(ptr), on_device, int(N), int(D), float(pval), int(min_pnum),
+            int(k), lam.ctypes.data_as(dp), vec.ctypes.data_as(dp), C.c_void_p(stream)))
+        del keep
+        return lam, vec
+
+    def last_stats(self):
+        """(outer passes, block Laplacian products) of the last eigs / spectral_embed."""
+        p, a = C.c_int32(), C.c_int64()
+        self._check(self.lib.zasr_diar_last_stats(self.handle, C.byref(p), C.byref(a)))
+        return int(p.value), int(a.value)

@@ -124,8 +124,14 @@ class FullPipe:
     def __init__(self, rec, recd, emb, vib, vib_vocab: int, beam: int = 1,
                  campp_batch: int = 4096, iterations: int = ITERATIONS, vib_batch: int = 0,
                  tokenizer=None, confidence: float = 0.3, case_confidence: float = 0.0,
-                 shard: bool = False):
-        """shard: strong scaling over the ranks of an initialised torch.distributed group (one
+                 shard: bool = False, diarize: bool = False):
+        """diarize: cluster each pass's window embeddings into speakers (zasr.diarize: the
+        reference's process() from the clustering on, :726-830) and add "speaker_segments"
+        (who spoke when: [{"start", "end", "speaker"}]) and "speaker_labels" (one per window)
+        to the pass's dict.  The spectral embedding runs on the CAM++ stream straight from the
+        device embeddings (with `shard`, from the gathered embeddings on every rank).
+
+        shard: strong scaling over the ranks of an initialised torch.distributed group (one
         process per GPU, every rank given the same file): each rank decodes its
         zasr.shard.lpt_partition share of the chunk plan and embeds its share of the speech
         regions; the per-chunk words are gathered to every rank in chunk order and merged
@@ -136,6 +142,11 @@ class FullPipe:
         self.rec, self.recd, self.emb, self.vib = rec, recd, emb, vib
         self.vib_vocab, self.beam, self.B, self.iterations = vib_vocab, beam, campp_batch, iterations
         self.shard = bool(shard)
+        self.diar = None
+        if diarize:
+            import torch
+            from zasr.binding import Diarizer
+            self.diar = Diarizer(torch.cuda.current_device())
         # <= 0: one ViBERT run per iteration (make_punctuator)
         self.punct = make_punctuator(RowShardedSession(vib) if self.shard else vib, vib_vocab,
                                      tokenizer, vib_batch, iterations=iterations,
@@ -281,12 +292,32 @@ class FullPipe:
                                     if len(reg) else np.zeros(0, np.int64), first, nfr], 1)
                     if self.shard:
                         embs, win = self._gather_windows(embs, win)
-                    outs.append({"words": words, "tokens": tokens, "text": text,
-                                 "vibert_runs": runs, "vibert_rows": rows, "embeddings": embs,
-                                 "windows": win,
-                                 "token_ids": [r.token_ids.tolist()
-                                               for r in res_all[p * n:(p + 1) * n]]})
+                    out = {"words": words, "tokens": tokens, "text": text,
+                           "vibert_runs": runs, "vibert_rows": rows, "embeddings": embs,
+                           "windows": win,
+                           "token_ids": [r.token_ids.tolist()
+                                         for r in res_all[p * n:(p + 1) * n]]}
+                    if self.diar is not None:
+                        out["speaker_segments"], out["speaker_labels"] = self.speakers(embs, win)
+                    outs.append(out)
         return outs
+
+    def speakers(self, embs: np.ndarray, win: np.ndarray):
+        """(segments, labels) of one pass's windows (zasr.diarize.diarize).  One GPU: the
+        similarity kernel reads self.d_emb on the CAM++ stream (it normalises the rows itself,
+        so the host copy `embs` serves only the O(N D) host steps); sharded: the gathered host
+        embeddings are uploaded."""
+        from zasr.diarize import diarize
+        st = self.s_campp.cuda_stream
+
+        def embed(X, pval, min_pnum, k):
+            if self.shard:
+                return self.diar.spectral_embed(np.ascontiguousarray(X, np.float32), pval=pval,
+                                                min_pnum=min_pnum, k=k, stream=st)
+            return self.diar.spectral_embed(self.d_emb.data_ptr(), pval=pval, min_pnum=min_pnum,
+                                            k=k, N=X.shape[0], D=X.shape[1], stream=st)
+        return diarize(embs, win, self.r_off_all, self.r_len_all, self.n / 16000.0, embed=embed,
+                       return_labels=True)
 
     def _gather_windows(self, embs: np.ndarray, win: np.ndarray):
         """Every rank's window embeddings and (region, first frame, frames) rows, in region
