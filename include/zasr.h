@@ -412,6 +412,19 @@ int zasr_selftest_gemm_h3r(int32_t M, int32_t K, int32_t N, int32_t epi, const f
 int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const float* W1,
                          const float* b1, const float* W2, const float* b2,
                          const float* byp_orig, const float* byp_scale, float* X);
+/* The general projection GEMMs alone on one dense host problem (same conventions): mode
+   ZASR_PRECISION_FP32 -> gemm_f32, ZASR_PRECISION_BF16 -> gemm_bf16 (a_bf16 / c_bf16: A / C held
+   in bf16 on the device, A rounded to nearest even on upload, C widened on return),
+   ZASR_PRECISION_BF16X3 / BF16X6 / F16X3 -> gemm_x3 with 2 / 3 / the two fp16 pieces.  A [M][K],
+   W [N][K] (prepared as the model loader prepares a weight), bias [N] or null, aux [M][N] for
+   the multiply epilogues (epi 4; 5: rounded to bf16 on upload), byp_orig [M][N] + byp_scale [N]
+   or both null (the bypass_mid blend after epi 3), C [M][N] in / out (epi 8, GLU: [M][N / 2]).
+   epi is a GemmEpi value (csrc/gemm.h).  One call of the public entry point with lda = K,
+   ldc = the C width; the kernel is the one the shape reaches in a decode.  A combination the
+   entry point refuses returns ZASR_ERR_RUNTIME with its message. */
+int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t epi, int32_t a_bf16,
+                       int32_t c_bf16, const float* A, const float* W, const float* bias,
+                       const float* aux, const float* byp_orig, const float* byp_scale, float* C);
 /* The bf16 mode's fused FeedforwardModule alone on host operands (same conventions):
    X[R][D] += W2 SwooshL(W1 bf16(X) + b1) + b2 with W1 [F][D], W2 [D][F] rounded to bf16 and
    the hidden activation in bf16 (then the bypass_mid blend when byp_orig is given);

@@ -102,6 +102,16 @@ __device__ __forceinline__ float sigmoid_fast(float x) {
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+// The bypass blend on four channels: orig + (x - orig) * scale (a layer's bypass and bypass_mid,
+// a stack's output combiner), these f32 operations in this order wherever it is applied (the
+// separate pass and every epilogue that folds it in), so the results are bit-identical.
+__device__ __forceinline__ void bypass_mix(float4& v, const float4 b0, const float4 k) {
+  v.x = b0.x + (v.x - b0.x) * k.x;
+  v.y = b0.y + (v.y - b0.y) * k.y;
+  v.z = b0.z + (v.z - b0.z) * k.z;
+  v.w = b0.w + (v.w - b0.w) * k.w;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

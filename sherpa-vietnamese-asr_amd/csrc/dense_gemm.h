@@ -20,7 +20,6 @@ inline GemmParams dense_gemm_params(const float* W, const float* bias, int N, in
   p.M = p.max_M = M;
   p.N = N;
   p.K = K;
-  p.alpha = 1.f;
   return p;
 }
 

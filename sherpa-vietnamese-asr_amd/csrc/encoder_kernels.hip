@@ -473,10 +473,7 @@ __global__ void bypass_kernel(float* __restrict__ x, const float* __restrict__ o
   float4 v = reinterpret_cast<float4*>(x)[i];
   float4 o = reinterpret_cast<const float4*>(orig)[i];
   float4 k = reinterpret_cast<const float4*>(s)[c4];
-  v.x = o.x + (v.x - o.x) * k.x;
-  v.y = o.y + (v.y - o.y) * k.y;
-  v.z = o.z + (v.z - o.z) * k.z;
-  v.w = o.w + (v.w - o.w) * k.w;
+  bypass_mix(v, o, k);
   reinterpret_cast<float4*>(x)[i] = v;
 }
 
@@ -824,10 +821,8 @@ __global__ void stack_glue_kernel(const float* __restrict__ xd, const float* __r
       const int t = r - off_in[b];
       const float4 up = reinterpret_cast<const float4*>(xd)[(off_ds[b] + (t >> ds_shift)) * d4 + c4];
       const float4 k = reinterpret_cast<const float4*>(s)[c4];
-      y.x = o.x + (up.x - o.x) * k.x;
-      y.y = o.y + (up.y - o.y) * k.y;
-      y.z = o.z + (up.z - o.z) * k.z;
-      y.w = o.w + (up.w - o.w) * k.w;
+      y = up;
+      bypass_mix(y, o, k);
     }
     if (full != nullptr && c4 >= c04) reinterpret_cast<float4*>(full)[r * ldf4 + c4] = y;
   }
@@ -902,10 +897,8 @@ __global__ void seam_kernel(SeamArgs a) {
 #pragma unroll
       for (int u = 0; u < G; ++u) {
         const float4 o = y[u];
-        y[u].x = o.x + (up[u].x - o.x) * k.x;
-        y[u].y = o.y + (up[u].y - o.y) * k.y;
-        y[u].z = o.z + (up[u].z - o.z) * k.z;
-        y[u].w = o.w + (up[u].w - o.w) * k.w;
+        y[u] = up[u];
+        bypass_mix(y[u], o, k);
       }
     }
   }

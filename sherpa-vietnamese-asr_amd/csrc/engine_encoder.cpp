@@ -241,7 +241,6 @@ void Engine::nonlin_attention(const StackCtx& c, const DLayer& Ly, float* X, con
   p.sbn = R8;
   p.ldc = hid;
   p.N = hid;
-  p.alpha = 1.f;
   p.aux = h3 + 2 * hid;
   p.ldaux = 3 * hid;
   p.slices = c.nl_slices;
@@ -340,7 +339,6 @@ void Engine::frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_
   p.ldc = l.N;
   p.bias = l.b;
   p.N = l.N;
-  p.alpha = 1.f;
   prof_begin("frontend_conv");
   if (l.wh && (a_bf16 || c_bf16))
     gemm_bf16(p, l.wh, EPI_SWOOSHR, aload, st_, a_bf16, c_bf16);

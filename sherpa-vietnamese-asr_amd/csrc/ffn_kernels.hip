@@ -233,10 +233,7 @@ __global__ __launch_bounds__(256, (D <= 192 ? 2 : 1)) void ffn_fused_kernel(floa
       if (byp_orig != nullptr) {  // bypass_mid folded in (launch_bypass's formula)
         const float4 b0 = *reinterpret_cast<const float4*>(byp_orig + (long)tok * D + ch);
         const float4 k = *reinterpret_cast<const float4*>(byp_scale + ch);
-        v.x = b0.x + (v.x - b0.x) * k.x;
-        v.y = b0.y + (v.y - b0.y) * k.y;
-        v.z = b0.z + (v.z - b0.z) * k.z;
-        v.w = b0.w + (v.w - b0.w) * k.w;
+        bypass_mix(v, b0, k);
       }
       *reinterpret_cast<float4*>(xr + ch) = v;
     }
@@ -457,10 +454,7 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
         v.w += o[t][u][3] + bv[t].w;
         if (byp_orig != nullptr) {
           const float4 b0 = b0v[du][t], k = kv[t];
-          v.x = b0.x + (v.x - b0.x) * k.x;
-          v.y = b0.y + (v.y - b0.y) * k.y;
-          v.z = b0.z + (v.z - b0.z) * k.z;
-          v.w = b0.w + (v.w - b0.w) * k.w;
+          bypass_mix(v, b0, k);
         }
         *reinterpret_cast<float4*>(xr + ch) = v;
       }
@@ -486,10 +480,7 @@ __global__ __launch_bounds__(512, 1) void ffn_wide_kernel(float* __restrict__ X,
       if (byp_orig != nullptr) {
         const float4 b0 = *reinterpret_cast<const float4*>(byp_orig + tok * D + ch);
         const float4 k = *reinterpret_cast<const float4*>(byp_scale + ch);
-        v.x = b0.x + (v.x - b0.x) * k.x;
-        v.y = b0.y + (v.y - b0.y) * k.y;
-        v.z = b0.z + (v.z - b0.z) * k.z;
-        v.w = b0.w + (v.w - b0.w) * k.w;
+        bypass_mix(v, b0, k);
       }
       *reinterpret_cast<float4*>(xr + ch) = v;
     }
@@ -692,10 +683,7 @@ __global__ __launch_bounds__(512, 2) void ffn_rows_kernel(float* __restrict__ X,
           v.w += o[t][u][3] + bv[t].w;
           if (byp_orig != nullptr) {
             const float4 b0 = b0v[du][t], k = kv[t];
-            v.x = b0.x + (v.x - b0.x) * k.x;
-            v.y = b0.y + (v.y - b0.y) * k.y;
-            v.z = b0.z + (v.z - b0.z) * k.z;
-            v.w = b0.w + (v.w - b0.w) * k.w;
+            bypass_mix(v, b0, k);
           }
           *reinterpret_cast<float4*>(xr + ch) = v;
         }
@@ -1073,10 +1061,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __r
           v.w += o[t][u][3] * kF16LoInv + bv[t].w;
           if (byp_orig != nullptr) {
             const float4 b0 = b0v[du][t], k = kv[t];
-            v.x = b0.x + (v.x - b0.x) * k.x;
-            v.y = b0.y + (v.y - b0.y) * k.y;
-            v.z = b0.z + (v.z - b0.z) * k.z;
-            v.w = b0.w + (v.w - b0.w) * k.w;
+            bypass_mix(v, b0, k);
           }
           *reinterpret_cast<float4*>(xr + ch) = v;
         }
@@ -1101,10 +1086,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void ffn_wide_h3_kernel(float* __r
       if (byp_orig != nullptr) {
         const float4 b0 = *reinterpret_cast<const float4*>(byp_orig + tok * D + ch);
         const float4 k = *reinterpret_cast<const float4*>(byp_scale + ch);
-        v.x = b0.x + (v.x - b0.x) * k.x;
-        v.y = b0.y + (v.y - b0.y) * k.y;
-        v.z = b0.z + (v.z - b0.z) * k.z;
-        v.w = b0.w + (v.w - b0.w) * k.w;
+        bypass_mix(v, b0, k);
       }
       *reinterpret_cast<float4*>(xr + ch) = v;
     }

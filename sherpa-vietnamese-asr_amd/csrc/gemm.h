@@ -1,9 +1,9 @@
 // Dense projection GEMMs of the Zipformer transducer on CDNA4 MFMA.
 //
-//   C[m, n] = epi( alpha * sum_k A'[m, k] * B[k, n] + bias[n] )
+//   C[m, n] = epi( sum_k A'[m, k] * B[k, n] + bias[n] )
 //
-// A' is produced by an A-loader (plain row-major activations, the joiner's
-// tanh(enc + dec) prologue, or implicit im2col for the Conv2dSubsampling convs), B is a
+// A' is produced by an A-loader (plain row-major activations, implicit im2col for the
+// Conv2dSubsampling and CAM++ convs, or a folded BatchNorm + ReLU), B is a
 // weight matrix [N][K] (K contiguous, the nn.Linear layout) or an activation matrix [K][N]
 // (N contiguous: the attention values).  Batched launches carry one descriptor per
 // z-slice (a sequence, or a (sequence, head) pair) so ragged sequences never pad.
@@ -29,7 +29,6 @@ enum GemmEpi : int {
 
 enum GemmALoad : int {
   ALOAD_DENSE = 0,   // A[m * lda + k]
-  ALOAD_JOINER = 1,  // retired (the joiner has its own split-K kernels)
   ALOAD_CONV2 = 2,   // im2col of conv1 output [T1][80][8]   -> conv.4 (3x3, stride 2)
   ALOAD_CONV3 = 3,   // im2col of conv2 output [L2][39][32]  -> conv.7 (3x3, stride (1,2))
   ALOAD_BNRELU = 4,  // max(A[m * lda + k] * a_scale[k] + a_shift[k], 0)  (gemm_f32 only)
@@ -53,15 +52,6 @@ struct GemmSlice {
   int pad_;
 };
 
-struct JoinerALoad {
-  const float* enc;      // [sum T', D]
-  const float* dec;      // [S*H, D]
-  const int* enc_off;    // [S] first encoder row of stream s
-  const int* enc_len;    // [S] T'_s
-  int H;                 // hyp slots per stream
-  int t;                 // current frame
-};
-
 struct GemmParams {
   const float* A;
   int lda;
@@ -73,7 +63,6 @@ struct GemmParams {
   const float* aux;      // EPI_MULAUX operand
   int ldaux;
   int M, N, K;
-  float alpha;
   const GemmSlice* slices;  // nullptr => single problem with the fields above
   int num_slices;
   int max_M;                // max M over slices (grid sizing)
@@ -81,7 +70,6 @@ struct GemmParams {
   // C = orig + (C - orig) * scale[n] (orig row stride ldc)
   const float* byp_orig = nullptr;
   const float* byp_scale = nullptr;
-  JoinerALoad joiner;
   const float* a_scale = nullptr;  // ALOAD_BNRELU
   const float* a_shift = nullptr;
   GemmIm2col1d i2c;                // ALOAD_IM2COL1D

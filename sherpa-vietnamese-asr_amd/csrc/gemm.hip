@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_f32_kernel(GemmPar
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (row >= M) continue;
-        float v = acc[i][j][r] * p.alpha + bcol;
+        float v = acc[i][j][r] + bcol;
         float* dst = C + (long)row * p.ldc + col;
         if constexpr (EPI == EPI_SWOOSHL) v = swooshl(v);
         if constexpr (EPI == EPI_SWOOSHR) v = swooshr(v);
@@ -231,12 +231,7 @@ void launch_t(const GemmParams& p, hipStream_t st) {
 
 template <int ALOAD, bool BNC, int EPI>
 void launch_tile(const GemmParams& p, hipStream_t st) {
-  // BN: the largest of {128, 64, 32} whose padded width is within 15% of the tightest.
-  int pad128 = cdiv(p.N, 128) * 128, pad64 = cdiv(p.N, 64) * 64, pad32 = cdiv(p.N, 32) * 32;
-  int best = pad32;
-  int BN = (pad128 * 100 <= best * 115) ? 128 : (pad64 * 100 <= best * 115 ? 64 : 32);
-  long blocks128 = (long)cdiv(p.max_M, 128) * cdiv(p.N, BN) * (p.slices ? p.num_slices : 1);
-  bool big = blocks128 >= 512;
+  const auto [BN, big] = pick_tile(p);
   if (BN == 128) {
     if (big) launch_t<128, 128, 2, 2, ALOAD, BNC, EPI>(p, st);
     else launch_t<64, 128, 2, 2, ALOAD, BNC, EPI>(p, st);
@@ -298,13 +293,6 @@ __device__ __forceinline__ bf16x8 load_a8(const GemmParams& p, const TA* A, int 
   return v;
 }
 
-template <int EPI>
-__device__ __forceinline__ float epi_act(float v) {
-  if constexpr (EPI == EPI_SWOOSHL) return swooshl_fast(v);
-  if constexpr (EPI == EPI_SWOOSHR) return swooshr_fast(v);
-  return v;
-}
-
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int ALOAD, int EPI, typename TA,
           typename TC, bool DEEP>
 // 8-wave tiles: hold 4 waves per SIMD (<= 128 VGPRs, two blocks per CU); at 130 VGPRs the
@@ -327,7 +315,7 @@ __attribute__((amdgpu_waves_per_eu(WAVES_M * WAVES_N >= 8 ? 4 : 1))) void gemm_b
   constexpr int A_LD = (A_G + NT - 1) / NT;
   constexpr int B_LD = (B_G + NT - 1) / NT;
   constexpr int STAGE = (BM + BN) * LDH;  // bf16 elements
-  constexpr int LDE = 40;                 // epilogue fragment row stride (floats)
+  constexpr int LDE = kEpiLd;             // epilogue fragment row stride (floats)
   // bf16 C without side inputs: two adjacent 32x32 fragments go through LDS together so that
   // every row segment is one 128-byte line written by 8 lanes x 16 bytes (one fragment alone
   // gives 64-byte half lines of 8-byte stores)
@@ -596,14 +584,14 @@ __attribute__((amdgpu_waves_per_eu(WAVES_M * WAVES_N >= 8 ? 4 : 1))) void gemm_b
             const float4 v1 = *reinterpret_cast<const float4*>(&sP[rl * LDE2 + 8 * c8 + 4]);
             if (row < M && col < N) {
               bf16x8 hv;
-              hv[0] = (__bf16)epi_act<EPI>(fmaf(v0.x, p.alpha, b0.x));
-              hv[1] = (__bf16)epi_act<EPI>(fmaf(v0.y, p.alpha, b0.y));
-              hv[2] = (__bf16)epi_act<EPI>(fmaf(v0.z, p.alpha, b0.z));
-              hv[3] = (__bf16)epi_act<EPI>(fmaf(v0.w, p.alpha, b0.w));
-              hv[4] = (__bf16)epi_act<EPI>(fmaf(v1.x, p.alpha, b1.x));
-              hv[5] = (__bf16)epi_act<EPI>(fmaf(v1.y, p.alpha, b1.y));
-              hv[6] = (__bf16)epi_act<EPI>(fmaf(v1.z, p.alpha, b1.z));
-              hv[7] = (__bf16)epi_act<EPI>(fmaf(v1.w, p.alpha, b1.w));
+              hv[0] = (__bf16)epi_act<EPI>(v0.x + b0.x);
+              hv[1] = (__bf16)epi_act<EPI>(v0.y + b0.y);
+              hv[2] = (__bf16)epi_act<EPI>(v0.z + b0.z);
+              hv[3] = (__bf16)epi_act<EPI>(v0.w + b0.w);
+              hv[4] = (__bf16)epi_act<EPI>(v1.x + b1.x);
+              hv[5] = (__bf16)epi_act<EPI>(v1.y + b1.y);
+              hv[6] = (__bf16)epi_act<EPI>(v1.z + b1.z);
+              hv[7] = (__bf16)epi_act<EPI>(v1.w + b1.w);
               *reinterpret_cast<bf16x8*>(C + (long)row * p.ldc + col) = hv;
             }
           }
@@ -613,89 +601,11 @@ __attribute__((amdgpu_waves_per_eu(WAVES_M * WAVES_N >= 8 ? 4 : 1))) void gemm_b
       return;
     }
   }
-  // epilogue: fragment -> LDS (lane: column lane&31, rows (r&3)+8(r>>2)+4(lane>>5)) ->
-  // float4 rows (8 lanes per 32-column row)
-  float* sE = reinterpret_cast<float*>(smem) + wid * (32 * LDE);
-  const int c4 = lane & 7;
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        sE[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * LDE + (lane & 31)] = acc[i][j][r];
-      __builtin_amdgcn_wave_barrier();
-      const int col = n0 + wn * WTN + j * 32 + 4 * c4;
-      float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias && col < N) bias = *reinterpret_cast<const float4*>(p.bias + col);
-      // residual-epilogue side inputs: unconditional (clamped) loads, all in flight before
-      // the guarded stores (a guarded load compiles to a branch with its own vmcnt(0))
-      float4 pre_o[4], pre_b[4], pre_k = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (EPI == EPI_RESADD && std::is_same<TC, float>::value) {
-        const int cc = col < N ? col : N - 4;
-        if (p.byp_orig != nullptr) pre_k = *reinterpret_cast<const float4*>(p.byp_scale + cc);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = m0 + wm * WTM + i * 32 + (lane >> 3) + 8 * q;
-          const long off = (long)(row < M ? row : M - 1) * p.ldc + cc;
-          pre_o[q] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(C) + off);
-          if (p.byp_orig != nullptr) pre_b[q] = *reinterpret_cast<const float4*>(p.byp_orig + off);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = (lane >> 3) + 8 * q;
-        const int row = m0 + wm * WTM + i * 32 + rl;
-        float4 v = *reinterpret_cast<const float4*>(&sE[rl * LDE + 4 * c4]);
-        if (row < M && col < N) {
-          v.x = epi_act<EPI>(fmaf(v.x, p.alpha, bias.x));
-          v.y = epi_act<EPI>(fmaf(v.y, p.alpha, bias.y));
-          v.z = epi_act<EPI>(fmaf(v.z, p.alpha, bias.z));
-          v.w = epi_act<EPI>(fmaf(v.w, p.alpha, bias.w));
-          if constexpr (EPI == EPI_MULAUX) {
-            const float4 x = *reinterpret_cast<const float4*>(aux + (long)row * p.ldaux + col);
-            v.x *= x.x; v.y *= x.y; v.z *= x.z; v.w *= x.w;
-          }
-          if constexpr (EPI == EPI_MULAUX16) {
-            const bf16x4 x = *reinterpret_cast<const bf16x4*>(aux16 + (long)row * p.ldaux + col);
-            v.x *= (float)x[0]; v.y *= (float)x[1]; v.z *= (float)x[2]; v.w *= (float)x[3];
-          }
-          if constexpr (EPI == EPI_GLU) {  // columns (2c, 2c + 1) -> channel c
-            const float g0 = v.x * sigmoid_fast(v.y), g1 = v.z * sigmoid_fast(v.w);
-            TC* dst = C + (long)row * p.ldc + col / 2;
-            if constexpr (std::is_same<TC, float>::value) {
-              *reinterpret_cast<float2*>(dst) = make_float2(g0, g1);
-            } else {
-              bf16x2 h;
-              h[0] = (__bf16)g0; h[1] = (__bf16)g1;
-              *reinterpret_cast<bf16x2*>(dst) = h;
-            }
-            continue;
-          }
-          TC* dst = C + (long)row * p.ldc + col;
-          if constexpr (std::is_same<TC, float>::value) {
-            if constexpr (EPI == EPI_RESADD) {
-              const float4 o = pre_o[q];
-              v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-              if (p.byp_orig != nullptr) {  // bypass_mid folded in (launch_bypass's formula)
-                const float4 b0 = pre_b[q];
-                v.x = b0.x + (v.x - b0.x) * pre_k.x;
-                v.y = b0.y + (v.y - b0.y) * pre_k.y;
-                v.z = b0.z + (v.z - b0.z) * pre_k.z;
-                v.w = b0.w + (v.w - b0.w) * pre_k.w;
-              }
-            }
-            *reinterpret_cast<float4*>(dst) = v;
-          } else {
-            bf16x4 h;
-            h[0] = (__bf16)v.x; h[1] = (__bf16)v.y; h[2] = (__bf16)v.z; h[3] = (__bf16)v.w;
-            *reinterpret_cast<bf16x4*>(dst) = h;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+  tile_epilogue<EPI, TC, FM, FN>(C, p.ldc, M, N, p.bias,
+                                 EPI == EPI_MULAUX16 ? (const void*)aux16 : (const void*)aux,
+                                 p.ldaux, p.byp_orig, p.byp_scale,
+                                 reinterpret_cast<float*>(smem) + wid * (32 * LDE), m0 + wm * WTM,
+                                 n0 + wn * WTN, lane, acc);
 }
 
 // gemm_set_deep(0) turns the two-slab register prefetch off (the labs' A/B switch)
@@ -718,14 +628,9 @@ void launch_h(const GemmParams& p, const __bf16* Bw, hipStream_t st) {
 
 template <int BK, int ALOAD, int EPI, typename TA, typename TC>
 void launch_tile_h(const GemmParams& p, const __bf16* Bw, hipStream_t st) {
-  int pad128 = cdiv(p.N, 128) * 128, pad64 = cdiv(p.N, 64) * 64, pad32 = cdiv(p.N, 32) * 32;
-  int best = pad32;
-  int BN = (pad128 * 100 <= best * 115) ? 128 : (pad64 * 100 <= best * 115 ? 64 : 32);
   // the sliced NonlinAttention GEMM streams a K = L-deep A panel per N tile: a 32-wide tile
   // re-reads it N/32 times at one MFMA per wave per k-step -- take 64 despite the padding
-  if ((EPI == EPI_MULAUX || EPI == EPI_MULAUX16) && BN == 32 && p.N > 64) BN = 64;
-  long blocks128 = (long)cdiv(p.max_M, 128) * cdiv(p.N, BN) * (p.slices ? p.num_slices : 1);
-  bool big = blocks128 >= 512;
+  const auto [BN, big] = pick_tile(p, EPI == EPI_MULAUX || EPI == EPI_MULAUX16);
   // wide tiles: 128 x 256 on 8 waves (2 x 4, 64 x 64 each) for N >= 256 -- twice the MFMAs
   // per A slab and per barrier of the 128 x 128 kernel, each A row panel read by half as many
   // blocks; measured -5 % enc_gemm time at the bench's shapes (profiles/r01/v15_gemm_tiles.txt).
@@ -790,7 +695,7 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmParams p, const __bf
   constexpr int GA = A_BYTES / 1024 / 4;  // DMA instructions per wave per slab
   constexpr int GB = B_BYTES / 1024 / 4;
   constexpr int G = GA + GB;
-  constexpr int LDE = 40;
+  constexpr int LDE = kEpiLd;
   constexpr int EPI_BYTES = 4 * 32 * LDE * 4;
   constexpr int LDS_BYTES = NS * STAGE > EPI_BYTES ? NS * STAGE : EPI_BYTES;
   static_assert(NS >= 2 && NS <= 4, "stages");
@@ -910,84 +815,9 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmParams p, const __bf
   }
   __syncthreads();  // every DMA retired (vmcnt(0) above) and every stage read: reuse smem
 
-  // epilogue: as gemm_bf16_kernel (fragment -> LDS -> float4 rows)
-  float* sE = reinterpret_cast<float*>(smem) + wid * (32 * LDE);
-  const int c4 = lane & 7;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        sE[((r & 3) + 8 * (r >> 2) + 4 * h) * LDE + r32] = acc[i][j][r];
-      __builtin_amdgcn_wave_barrier();
-      const int col = n0 + wn * (BN / 2) + j * 32 + 4 * c4;
-      float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias && col < N) bias = *reinterpret_cast<const float4*>(p.bias + col);
-      // residual-epilogue side inputs: unconditional (clamped) loads, all in flight before
-      // the guarded stores (a guarded load compiles to a branch with its own vmcnt(0))
-      float4 pre_o[4], pre_b[4], pre_k = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (EPI == EPI_RESADD && std::is_same<TC, float>::value) {
-        const int cc = col < N ? col : N - 4;
-        if (p.byp_orig != nullptr) pre_k = *reinterpret_cast<const float4*>(p.byp_scale + cc);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = m0 + wm * 64 + i * 32 + (lane >> 3) + 8 * q;
-          const long off = (long)(row < M ? row : M - 1) * p.ldc + cc;
-          pre_o[q] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(C) + off);
-          if (p.byp_orig != nullptr) pre_b[q] = *reinterpret_cast<const float4*>(p.byp_orig + off);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = (lane >> 3) + 8 * q;
-        const int row = m0 + wm * 64 + i * 32 + rl;
-        float4 v = *reinterpret_cast<const float4*>(&sE[rl * LDE + 4 * c4]);
-        if (row < M && col < N) {
-          v.x = epi_act<EPI>(fmaf(v.x, p.alpha, bias.x));
-          v.y = epi_act<EPI>(fmaf(v.y, p.alpha, bias.y));
-          v.z = epi_act<EPI>(fmaf(v.z, p.alpha, bias.z));
-          v.w = epi_act<EPI>(fmaf(v.w, p.alpha, bias.w));
-          if constexpr (EPI == EPI_MULAUX16) {
-            const bf16x4 x = *reinterpret_cast<const bf16x4*>(aux16 + (long)row * p.ldaux + col);
-            v.x *= (float)x[0]; v.y *= (float)x[1]; v.z *= (float)x[2]; v.w *= (float)x[3];
-          }
-          if constexpr (EPI == EPI_GLU) {  // columns (2c, 2c + 1) -> channel c
-            const float g0 = v.x * sigmoid_fast(v.y), g1 = v.z * sigmoid_fast(v.w);
-            TC* dst = C + (long)row * p.ldc + col / 2;
-            if constexpr (std::is_same<TC, float>::value) {
-              *reinterpret_cast<float2*>(dst) = make_float2(g0, g1);
-            } else {
-              bf16x2 h;
-              h[0] = (__bf16)g0; h[1] = (__bf16)g1;
-              *reinterpret_cast<bf16x2*>(dst) = h;
-            }
-            continue;
-          }
-          TC* dst = C + (long)row * p.ldc + col;
-          if constexpr (std::is_same<TC, float>::value) {
-            if constexpr (EPI == EPI_RESADD) {
-              const float4 o = pre_o[q];
-              v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-              if (p.byp_orig != nullptr) {  // bypass_mid folded in (launch_bypass's formula)
-                const float4 b0 = pre_b[q];
-                v.x = b0.x + (v.x - b0.x) * pre_k.x;
-                v.y = b0.y + (v.y - b0.y) * pre_k.y;
-                v.z = b0.z + (v.z - b0.z) * pre_k.z;
-                v.w = b0.w + (v.w - b0.w) * pre_k.w;
-              }
-            }
-            *reinterpret_cast<float4*>(dst) = v;
-          } else {
-            bf16x4 hv;
-            hv[0] = (__bf16)v.x; hv[1] = (__bf16)v.y; hv[2] = (__bf16)v.z; hv[3] = (__bf16)v.w;
-            *reinterpret_cast<bf16x4*>(dst) = hv;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+  tile_epilogue<EPI, TC, 2, FN>(C, p.ldc, M, N, p.bias, aux16, p.ldaux, p.byp_orig, p.byp_scale,
+                                reinterpret_cast<float*>(smem) + wid * (32 * kEpiLd),
+                                m0 + wm * 64, n0 + wn * (BN / 2), lane, acc);
 }
 
 template <int NS, int EPI, typename TA, typename TC>

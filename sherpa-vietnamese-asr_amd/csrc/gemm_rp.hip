@@ -22,15 +22,11 @@
 
 #include "common.h"
 #include "gemm.h"
+#include "gemm_dev.h"
 
 namespace zasr {
 
 namespace rp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BM = 64;
 constexpr int CHUNK = 128;  // columns per sweep step (4 waves x 32)
@@ -46,13 +42,6 @@ constexpr int ring_depth(int qk) {
   for (int p = 8; p >= 2; --p)
     if (qk % p == 0) return p;
   return 1;
-}
-
-template <int EPI>
-__device__ __forceinline__ float act(float v) {
-  if constexpr (EPI == EPI_SWOOSHL) return swooshl_fast(v);
-  if constexpr (EPI == EPI_SWOOSHR) return swooshr_fast(v);
-  return v;
 }
 
 template <int K, typename TA, typename TC, int EPI>
@@ -170,7 +159,7 @@ __global__ __launch_bounds__(256) void gemm_rp_kernel(const TA* __restrict__ A, 
       if constexpr (std::is_same<TC, float>::value) {
         float v[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = act<EPI>(acc[r] + bc);
+        for (int r = 0; r < 16; ++r) v[r] = epi_act<EPI>(acc[r] + bc);
         if constexpr (EPI == EPI_RESADD) {
           float o[16];
 #pragma unroll
@@ -192,8 +181,8 @@ __global__ __launch_bounds__(256) void gemm_rp_kernel(const TA* __restrict__ A, 
         const bool odd = (lane & 1) != 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const float e = act<EPI>(acc[2 * i] + bc);
-          const float o = act<EPI>(acc[2 * i + 1] + bc);
+          const float e = epi_act<EPI>(acc[2 * i] + bc);
+          const float o = epi_act<EPI>(acc[2 * i + 1] + bc);
           const float x = __shfl_xor(odd ? e : o, 1, 64);
           bf16x2 pr;
           pr[0] = (__bf16)(odd ? x : e);
@@ -276,7 +265,7 @@ void gemm_rp_pack_weights(const void* W, int N, int K, void* out, hipStream_t st
   const long n = (long)ngroups * (K / 16) * 64;
   ZASR_LAUNCH(rp::permute_rp_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, st,
                      reinterpret_cast<const __bf16*>(W), N, K, ngroups,
-                     reinterpret_cast<rp::bf16x8*>(out));
+                     reinterpret_cast<bf16x8*>(out));
 }
 
 bool gemm_rp(const void* A, bool a_bf16, int lda, const void* Bp, const float* bias, void* C,

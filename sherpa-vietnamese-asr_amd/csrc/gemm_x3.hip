@@ -17,7 +17,7 @@
 // slabs staged through LDS as row-major [row][BK + 8] bf16 images (hi and lo of A and of W),
 // two LDS stages, next slab's global loads in registers under the MFMAs (two register sets
 // when K is a multiple of 64), tiles numbered so that blocks sharing an A row panel land on
-// one XCD, epilogue through LDS as float4 rows.
+// one XCD, epilogue through LDS as float4 rows (gemm_dev.h tile_epilogue).
 #include <type_traits>
 
 #include "common.h"
@@ -26,45 +26,6 @@
 
 namespace zasr {
 namespace {
-
-// x -> NP bf16 pieces p0 + p1 (+ p2), each the RNE bf16 of what the previous ones left
-template <int NP>
-__device__ __forceinline__ void split8(const float4 x0, const float4 x1, bf16x8 (&pc)[NP]) {
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    float r = v[q];
-#pragma unroll
-    for (int t = 0; t < NP; ++t) {
-      const __bf16 h = (__bf16)r;
-      pc[t][q] = h;
-      if (t + 1 < NP) r -= (float)h;
-    }
-  }
-}
-
-// native exp2 / log forms (common.h; ~1e-7 absolute from the libm forms, below the f32
-// rounding of the values they feed): the libm log1pf(expf()) pair made the SwooshL-epilogue
-// shapes 2-3x slower than the plain ones (profiles/r03/x3_shape_table.json)
-// EPI_RESADD with p.byp_orig: the layer's bypass_mid folded in after the residual add,
-// launch_bypass's formula (orig + (x - orig) * scale), the same f32 operations in the same
-// order, so the result is bit-identical to the separate pass
-__device__ __forceinline__ void x3_bypass(const GemmParams& p, float4& v, int row, int col) {
-  if (p.byp_orig == nullptr) return;
-  const float4 b0 = *reinterpret_cast<const float4*>(p.byp_orig + (long)row * p.ldc + col);
-  const float4 k = *reinterpret_cast<const float4*>(p.byp_scale + col);
-  v.x = b0.x + (v.x - b0.x) * k.x;
-  v.y = b0.y + (v.y - b0.y) * k.y;
-  v.z = b0.z + (v.z - b0.z) * k.z;
-  v.w = b0.w + (v.w - b0.w) * k.w;
-}
-
-template <int EPI>
-__device__ __forceinline__ float x3_act(float v) {
-  if constexpr (EPI == EPI_SWOOSHL) return swooshl_fast(v);
-  if constexpr (EPI == EPI_SWOOSHR) return swooshr_fast(v);
-  return v;
-}
 
 // NP = 2 ("bf16x3"): pieces (hi, lo), products p0q0 + p0q1 + p1q0 (3 MFMAs), BK = 32.
 // NP = 3 ("bf16x6"): pieces (p0, p1, p2), the six products p_i q_j with i + j <= 2 (6 MFMAs,
@@ -92,7 +53,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N,
   constexpr int B_LD = (B_G + NT - 1) / NT;
   // stage: A pieces [NP][BM][LDH], then W pieces [NP][BN][LDH]
   constexpr int STAGE = NP * (BM + BN) * LDH;
-  constexpr int LDE = 40;
+  constexpr int LDE = kEpiLd;
   constexpr int OPER_BYTES = 2 * STAGE * 2;
   constexpr int EPI_BYTES = (NT / 64) * 32 * LDE * 4;
   constexpr int LDS_BYTES = OPER_BYTES > EPI_BYTES ? OPER_BYTES : EPI_BYTES;
@@ -315,62 +276,9 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N,
     }
   }
 
-  // epilogue: fragment -> LDS (lane: column lane&31, rows (r&3)+8(r>>2)+4(lane>>5)) ->
-  // float4 rows (8 lanes per 32-column row); side inputs loaded unconditionally (clamped)
-  float* sE = reinterpret_cast<float*>(smem) + wid * (32 * LDE);
-  const int c4 = lane & 7;
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        sE[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * LDE + (lane & 31)] =
-            FMT == 1 ? acc[i][j][r] + accl[i % FL][j % FLN][r] * kF16LoInv : acc[i][j][r];
-      __builtin_amdgcn_wave_barrier();
-      const int col = n0 + wn * WTN + j * 32 + 4 * c4;
-      const int cc = col < N ? col : N - 4;
-      float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias) bias = *reinterpret_cast<const float4*>(p.bias + cc);
-      float4 side[4];
-      if constexpr (EPI == EPI_RESADD || EPI == EPI_MULAUX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = m0 + wm * WTM + i * 32 + (lane >> 3) + 8 * q;
-          const int rc = row < M ? row : M - 1;
-          side[q] = EPI == EPI_RESADD
-                        ? *reinterpret_cast<const float4*>(C + (long)rc * p.ldc + cc)
-                        : *reinterpret_cast<const float4*>(aux + (long)rc * p.ldaux + cc);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = (lane >> 3) + 8 * q;
-        const int row = m0 + wm * WTM + i * 32 + rl;
-        float4 v = *reinterpret_cast<const float4*>(&sE[rl * LDE + 4 * c4]);
-        if (row < M && col < N) {
-          v.x = x3_act<EPI>(v.x + bias.x);
-          v.y = x3_act<EPI>(v.y + bias.y);
-          v.z = x3_act<EPI>(v.z + bias.z);
-          v.w = x3_act<EPI>(v.w + bias.w);
-          if constexpr (EPI == EPI_RESADD) {
-            v.x += side[q].x; v.y += side[q].y; v.z += side[q].z; v.w += side[q].w;
-            x3_bypass(p, v, row, col);
-          }
-          if constexpr (EPI == EPI_MULAUX) {
-            v.x *= side[q].x; v.y *= side[q].y; v.z *= side[q].z; v.w *= side[q].w;
-          }
-          if constexpr (EPI == EPI_GLU) {  // columns (2c, 2c + 1) -> channel c
-            *reinterpret_cast<float2*>(C + (long)row * p.ldc + col / 2) =
-                make_float2(v.x * sigmoid_fast(v.y), v.z * sigmoid_fast(v.w));
-          } else {
-            *reinterpret_cast<float4*>(C + (long)row * p.ldc + col) = v;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+  tile_epilogue<EPI, float, FMT == 1>(C, p.ldc, M, N, p.bias, aux, p.ldaux, p.byp_orig, p.byp_scale,
+                                      reinterpret_cast<float*>(smem) + wid * (32 * LDE),
+                                      m0 + wm * WTM, n0 + wn * WTN, lane, acc, accl);
 }
 
 template <int BM, int BN, int WM, int WN, int ALOAD, int EPI, int NP, int BK = (NP == 2 ? 32 : 16),
@@ -399,73 +307,6 @@ void launch_x3_t(const GemmParams& p, const __bf16* Bw, long blo, hipStream_t st
 // ---------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* h3_lds_t;
 
-// f16x3 epilogue of the LDS-DMA kernels (gemm_x3_kernel's): per 32 x 32 fragment, hi + lo *
-// 2^-11 -> the wave's LDS slice sE (32 x 40 floats) -> float4 rows with bias, activation and
-// the side input (rows clamped for the side loads, stores guarded).  row0 / col0: the wave's
-// first output row / column.
-template <int EPI, int FM, int FN>
-__device__ __forceinline__ void h3_epilogue(const GemmParams& p, float* sE,
-                                            const f32x16 (&acc)[FM][FN],
-                                            const f32x16 (&accl)[FM][FN], int row0, int col0,
-                                            int lane) {
-  constexpr int LDE = 40;
-  const int M = p.M, N = p.N;
-  const int r32 = lane & 31, h = lane >> 5, c4 = lane & 7;
-  float* C = p.C;
-  const float* aux = p.aux;
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        sE[((r & 3) + 8 * (r >> 2) + 4 * h) * LDE + r32] = acc[i][j][r] + accl[i][j][r] * kF16LoInv;
-      __builtin_amdgcn_wave_barrier();
-      const int col = col0 + j * 32 + 4 * c4;
-      const int cc = col < N ? col : N - 4;
-      float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias) bias = *reinterpret_cast<const float4*>(p.bias + cc);
-      float4 side[4];
-      if constexpr (EPI == EPI_RESADD || EPI == EPI_MULAUX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = row0 + i * 32 + (lane >> 3) + 8 * q;
-          const int rc = row < M ? row : M - 1;
-          side[q] = EPI == EPI_RESADD
-                        ? *reinterpret_cast<const float4*>(C + (long)rc * p.ldc + cc)
-                        : *reinterpret_cast<const float4*>(aux + (long)rc * p.ldaux + cc);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = (lane >> 3) + 8 * q;
-        const int row = row0 + i * 32 + rl;
-        float4 v = *reinterpret_cast<const float4*>(&sE[rl * LDE + 4 * c4]);
-        if (row < M && col < N) {
-          v.x = x3_act<EPI>(v.x + bias.x);
-          v.y = x3_act<EPI>(v.y + bias.y);
-          v.z = x3_act<EPI>(v.z + bias.z);
-          v.w = x3_act<EPI>(v.w + bias.w);
-          if constexpr (EPI == EPI_RESADD) {
-            v.x += side[q].x; v.y += side[q].y; v.z += side[q].z; v.w += side[q].w;
-            x3_bypass(p, v, row, col);
-          }
-          if constexpr (EPI == EPI_MULAUX) {
-            v.x *= side[q].x; v.y *= side[q].y; v.z *= side[q].z; v.w *= side[q].w;
-          }
-          if constexpr (EPI == EPI_GLU) {  // columns (2c, 2c + 1) -> channel c
-            *reinterpret_cast<float2*>(C + (long)row * p.ldc + col / 2) =
-                make_float2(v.x * sigmoid_fast(v.y), v.z * sigmoid_fast(v.w));
-          } else {
-            *reinterpret_cast<float4*>(C + (long)row * p.ldc + col) = v;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
 // PR = 1: the hi x hi product only (a diagnostic of the split_lab: what the loop costs
 // without the two correction MFMAs; not numerically a split GEMM)
 // ALD = ALOAD_CONV3 (Conv2dSubsampling's conv.7 as an implicit GEMM, K = 9 taps x 32
@@ -489,7 +330,7 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void gemm_glds_h3_kernel(Gemm
   constexpr int GA = A_BYTES / 1024 / 4;
   constexpr int GB = B_BYTES / 1024 / 4;
   constexpr int G = GA + 2 * GB;
-  constexpr int LDE = 40;
+  constexpr int LDE = kEpiLd;
   constexpr int EPI_BYTES = 4 * 32 * LDE * 4;
   constexpr int LDS_BYTES = NS * STAGE > EPI_BYTES ? NS * STAGE : EPI_BYTES;
   static_assert(NS >= 2 && NS <= 3, "stages");
@@ -639,8 +480,9 @@ __global__ __launch_bounds__(256, NS == 2 ? 2 : 1) void gemm_glds_h3_kernel(Gemm
   }
   __syncthreads();
 
-  h3_epilogue<EPI, FM, FN>(q, reinterpret_cast<float*>(smem) + wid * (32 * LDE), acc, accl,
-                           m0 + wm * WTM, n0 + wn * WTN, lane);
+  tile_epilogue<EPI, float, true>(q.C, q.ldc, M, N, q.bias, q.aux, q.ldaux, q.byp_orig, q.byp_scale,
+                                  reinterpret_cast<float*>(smem) + wid * (32 * LDE), m0 + wm * WTM,
+                                  n0 + wn * WTN, lane, acc, accl);
 }
 
 template <int NS, int EPI, int BN, int WM = 2, int PR = 3, int ALD = ALOAD_DENSE, int RB = 0>
@@ -676,10 +518,7 @@ void launch_h3(const GemmParams& p, const __bf16* Bw, long blo, hipStream_t st) 
       return launch_glds_h3<2, EPI, 64, 4, 3, ALOAD_DENSE, 1>(p, Bw, blo, st);
     }
   }
-  const int pad128 = cdiv(p.N, 128) * 128, pad64 = cdiv(p.N, 64) * 64, pad32 = cdiv(p.N, 32) * 32;
-  const int BN = (pad128 * 100 <= pad32 * 115) ? 128 : (pad64 * 100 <= pad32 * 115 ? 64 : 32);
-  const long blocks128 = (long)cdiv(p.max_M, 128) * cdiv(p.N, BN) * (p.slices ? p.num_slices : 1);
-  const bool big = blocks128 >= 512;
+  const auto [BN, big] = pick_tile(p);
   if (BN == 128) {
     if (big) launch_x3_t<128, 128, 2, 2, ALOAD, EPI, 2, 16, 1>(p, Bw, blo, st);
     else launch_x3_t<64, 128, 2, 2, ALOAD, EPI, 2, 16, 1>(p, Bw, blo, st);
@@ -694,11 +533,7 @@ void launch_h3(const GemmParams& p, const __bf16* Bw, long blo, hipStream_t st) 
 
 template <int ALOAD, int EPI, int NP>
 void launch_x3(const GemmParams& p, const __bf16* Bw, long blo, hipStream_t st) {
-  // BN: the largest of {128, 64, 32} whose padded width is within 15 % of the tightest
-  const int pad128 = cdiv(p.N, 128) * 128, pad64 = cdiv(p.N, 64) * 64, pad32 = cdiv(p.N, 32) * 32;
-  const int BN = (pad128 * 100 <= pad32 * 115) ? 128 : (pad64 * 100 <= pad32 * 115 ? 64 : 32);
-  const long blocks128 = (long)cdiv(p.max_M, 128) * cdiv(p.N, BN) * (p.slices ? p.num_slices : 1);
-  const bool big = blocks128 >= 512;
+  const auto [BN, big] = pick_tile(p);
   // 8-wave 128 x 256 / 256 x 128 tiles were 10-20 % faster alone (tools/x6_bench,
   // profiles/r03/split_gemm/x6_tile_lab_v1.txt) but slower under the batch pipeline, where
   // two encoder streams share the CUs (enc_gemm 55.7 -> 58.4 ms per step): 4-wave tiles

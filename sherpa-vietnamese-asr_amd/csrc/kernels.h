@@ -37,6 +37,11 @@ void launch_selftest_noop(int block_threads);
 // kernel self-tests on host operands (selftest.cpp; zasr_selftest_gemm_h3r / _ffn_h3 / _ffn_bf16)
 void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float* W,
                        const float* bias, float* C);
+// one dense problem through gemm_f32 / gemm_bf16 / gemm_x3 (mode: a ZASR_PRECISION_* value),
+// weights prepared as the loader does, lda = K, ldc = N (N / 2 for EPI_GLU); C in / out as f32
+void selftest_gemm(int mode, int M, int K, int N, int epi, bool a_bf16, bool c_bf16,
+                   const float* A, const float* W, const float* bias, const float* aux,
+                   const float* byp_orig, const float* byp_scale, float* C);
 void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const float* b1,
                      const float* W2, const float* b2, const float* byp_orig,
                      const float* byp_scale, float* X, float* Xout = nullptr);

@@ -1,14 +1,17 @@
-// Kernel-level self-tests on host data (include/zasr.h zasr_selftest_*): the f16x3
-// one-accumulator kernels and the bf16 fused FFN run alone on caller-supplied operands, so the tests can sweep the
-// shapes and row counts the decode only reaches incidentally (tail tiles, M < 16, every K / D
-// and epilogue) against a float64 product on the host; the fused FFNs also out of place, and
-// the fused stack seam beside the kernels it replaces.  Device 0 of the process, its null
-// stream, synchronous; nothing here is on the decode path.
+// Kernel-level self-tests on host data (include/zasr.h zasr_selftest_*): the general GEMM entry
+// points, the f16x3 one-accumulator kernels and the bf16 fused FFN run alone on caller-supplied
+// operands, so the tests can sweep the shapes and row counts the decode only reaches
+// incidentally (tail tiles, M < 16, every K / D and epilogue) against a float64 product on the
+// host; the fused FFNs also out of place, and the fused stack seam beside the kernels it
+// replaces.  Device 0 of the process, its null stream, synchronous; nothing here is on the
+// decode path.
 #include <cstring>
 #include <memory>
 #include <vector>
 
+#include "../../include/zasr.h"
 #include "common.h"
+#include "dense_gemm.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -43,6 +46,78 @@ void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float
            epi, nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   ZASR_HIP_CHECK(hipMemcpy(C, dC.p, (size_t)M * ncol * 4, hipMemcpyDeviceToHost));
+}
+
+void selftest_gemm(int mode, int M, int K, int N, int epi, bool a_bf16, bool c_bf16,
+                   const float* A, const float* W, const float* bias, const float* aux,
+                   const float* byp_orig, const float* byp_scale, float* C) {
+  const bool f32 = mode == ZASR_PRECISION_FP32, h16 = mode == ZASR_PRECISION_BF16;
+  const int pieces = mode == ZASR_PRECISION_BF16X3   ? 2
+                     : mode == ZASR_PRECISION_BF16X6 ? 3
+                     : mode == ZASR_PRECISION_F16X3  ? kPiecesF16
+                                                     : 0;
+  ZASR_REQUIRE(f32 || h16 || pieces != 0,
+               "selftest gemm: mode must be ZASR_PRECISION_FP32, _BF16, _BF16X3, _BF16X6 or _F16X3");
+  ZASR_REQUIRE(M >= 1 && K >= 1 && N >= 1, "selftest gemm: M, K, N >= 1");
+  ZASR_REQUIRE(h16 || (!a_bf16 && !c_bf16), "selftest gemm: bf16 A / C in the bf16 mode only");
+  const bool mulaux = epi == EPI_MULAUX || epi == EPI_MULAUX16;
+  ZASR_REQUIRE(!mulaux || aux != nullptr, "selftest gemm: EPI_MULAUX needs aux");
+  ZASR_REQUIRE((byp_orig == nullptr) == (byp_scale == nullptr) &&
+                   (byp_orig == nullptr || (epi == EPI_RESADD && !f32)),
+               "selftest gemm: the bypass takes both operands, EPI_RESADD, not the fp32 mode");
+  ZASR_REQUIRE(epi != EPI_GLU || N % 2 == 0, "selftest gemm: EPI_GLU needs an even N");
+  const int ncol = epi == EPI_GLU ? N / 2 : N;
+  const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * ncol, nx = (size_t)M * N;
+  const size_t ea = a_bf16 ? 2 : 4, ec = c_bf16 ? 2 : 4, ex = epi == EPI_MULAUX16 ? 2 : 4;
+  auto round16 = [](const float* s, size_t n) {
+    std::vector<__bf16> h(n);
+    for (size_t i = 0; i < n; ++i) h[i] = (__bf16)s[i];
+    return h;
+  };
+  DevBuf dA(na * ea), dW(nw * 4), dWx(nw * 2 * (pieces ? stored_pieces(pieces) : 1)), dB((size_t)N * 4),
+      dC((nc + ncol) * ec), dX(aux ? nx * ex : 4), dbo(byp_orig ? nc * 4 : 4), dbs((size_t)N * 4);
+  if (a_bf16) up(dA, round16(A, na).data(), na * 2);
+  else up(dA, A, na * 4);
+  up(dW, W, nw * 4);
+  // the weights as the loader prepares them (engine_load.cpp)
+  if (h16) convert_to_bf16(dW.as<float>(), dWx.p, (long)nw, nullptr);
+  if (pieces) split_to_bf16(dW.as<float>(), dWx.p, (long)nw, pieces, nullptr);
+  if (bias) up(dB, bias, (size_t)N * 4);
+  if (c_bf16) up(dC, round16(C, nc).data(), nc * 2);  // the RESADD operand / what stays unwritten
+  else up(dC, C, nc * 4);
+  // one guard row behind C: a store past the row tail must not reach it
+  const size_t gb = (size_t)ncol * ec;
+  ZASR_HIP_CHECK(hipMemset(dC.as<unsigned char>() + nc * ec, 0x5a, gb));
+  if (aux && epi == EPI_MULAUX16) up(dX, round16(aux, nx).data(), nx * 2);
+  else if (aux) up(dX, aux, nx * 4);
+  if (byp_orig) {
+    up(dbo, byp_orig, nc * 4);
+    up(dbs, byp_scale, (size_t)N * 4);
+  }
+  GemmParams p = dense_gemm_params(dW.as<float>(), bias ? dB.as<float>() : nullptr, N, K, dA.p, K, M,
+                                   dC.p, ncol);
+  if (aux) {
+    p.aux = dX.as<float>();
+    p.ldaux = N;
+  }
+  if (byp_orig) {
+    p.byp_orig = dbo.as<float>();
+    p.byp_scale = dbs.as<float>();
+  }
+  if (f32) gemm_f32(p, epi, ALOAD_DENSE, false, nullptr);
+  else if (h16) gemm_bf16(p, dWx.p, epi, ALOAD_DENSE, nullptr, a_bf16, c_bf16);
+  else gemm_x3(p, dWx.p, (long)nw, epi, ALOAD_DENSE, nullptr, pieces);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  std::vector<unsigned char> guard(gb);
+  ZASR_HIP_CHECK(hipMemcpy(guard.data(), dC.as<unsigned char>() + nc * ec, gb, hipMemcpyDeviceToHost));
+  for (unsigned char g : guard) ZASR_REQUIRE(g == 0x5a, "selftest gemm: the kernel wrote past row M of C");
+  if (c_bf16) {
+    std::vector<__bf16> h(nc);
+    ZASR_HIP_CHECK(hipMemcpy(h.data(), dC.p, nc * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nc; ++i) C[i] = (float)h[i];
+  } else {
+    ZASR_HIP_CHECK(hipMemcpy(C, dC.p, nc * 4, hipMemcpyDeviceToHost));
+  }
 }
 
 void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const float* b1,

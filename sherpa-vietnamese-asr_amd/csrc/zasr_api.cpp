@@ -685,6 +685,17 @@ int zasr_selftest_gemm_h3r(int32_t M, int32_t K, int32_t N, int32_t epi, const f
   });
 }
 
+int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t epi, int32_t a_bf16,
+                       int32_t c_bf16, const float* A, const float* W, const float* bias,
+                       const float* aux, const float* byp_orig, const float* byp_scale, float* C) {
+  if (!A || !W || !C) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_gemm(mode, M, K, N, epi, a_bf16 != 0, c_bf16 != 0, A, W, bias, aux, byp_orig,
+                        byp_scale, C);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const float* W1,
                          const float* b1, const float* W2, const float* b2,
                          const float* byp_orig, const float* byp_scale, float* X) {

@@ -33,7 +33,6 @@ static void run_variant(const char* tag, const Shape& s, float* dA, __bf16* dA16
   p.M = s.M;
   p.N = s.N;
   p.K = s.K;
-  p.alpha = 1.f;
   p.max_M = s.M;
   hipMemset(dC, 0, (size_t)s.M * s.N * 4);
   hipEvent_t a, b;

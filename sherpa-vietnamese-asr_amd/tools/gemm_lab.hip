@@ -682,7 +682,6 @@ static void run_shape(const Shape& s, void* dA, __bf16* dB, void* dC) {
   p.M = s.M;
   p.N = s.N;
   p.K = s.K;
-  p.alpha = 1.f;
   p.max_M = s.M;
   const double bytes = (double)s.M * s.K * sizeof(TA) + (double)s.N * s.K * 2 + (double)s.M * s.N * sizeof(TC);
   const double flops = 2.0 * s.M * s.K * s.N;

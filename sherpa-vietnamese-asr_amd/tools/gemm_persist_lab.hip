@@ -194,14 +194,14 @@ __attribute__((amdgpu_waves_per_eu(WAVES_M * WAVES_N >= 8 ? 4 : 2))) void gemm_p
           const float4 v1 = *reinterpret_cast<const float4*>(&sP[rl * LDE2 + 8 * c8 + 4]);
           if (row < M && col < N) {
             bf16x8 hv;
-            hv[0] = (__bf16)fmaf(v0.x, p.alpha, b0.x);
-            hv[1] = (__bf16)fmaf(v0.y, p.alpha, b0.y);
-            hv[2] = (__bf16)fmaf(v0.z, p.alpha, b0.z);
-            hv[3] = (__bf16)fmaf(v0.w, p.alpha, b0.w);
-            hv[4] = (__bf16)fmaf(v1.x, p.alpha, b1.x);
-            hv[5] = (__bf16)fmaf(v1.y, p.alpha, b1.y);
-            hv[6] = (__bf16)fmaf(v1.z, p.alpha, b1.z);
-            hv[7] = (__bf16)fmaf(v1.w, p.alpha, b1.w);
+            hv[0] = (__bf16)(v0.x + b0.x);
+            hv[1] = (__bf16)(v0.y + b0.y);
+            hv[2] = (__bf16)(v0.z + b0.z);
+            hv[3] = (__bf16)(v0.w + b0.w);
+            hv[4] = (__bf16)(v1.x + b1.x);
+            hv[5] = (__bf16)(v1.y + b1.y);
+            hv[6] = (__bf16)(v1.z + b1.z);
+            hv[7] = (__bf16)(v1.w + b1.w);
             *reinterpret_cast<bf16x8*>(C + (long)row * p.ldc + col) = hv;
           }
         }
@@ -295,7 +295,6 @@ int main() {
     p.M = s.M;
     p.N = s.N;
     p.K = s.K;
-    p.alpha = 1.f;
     p.max_M = s.M;
     launch_h<128, 128, 32, 2, 2, ALOAD_DENSE, EPI_NONE, float, __bf16>(p, dB, 0);
     const float t128 = time([&] { launch_h<128, 128, 32, 2, 2, ALOAD_DENSE, EPI_NONE, float, __bf16>(p, dB, 0); });

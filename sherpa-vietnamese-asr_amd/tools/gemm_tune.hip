@@ -41,7 +41,6 @@ static SweepResult sweep(const Shape& s) {
   p.M = s.M;
   p.N = s.N;
   p.K = s.K;
-  p.alpha = 1.f;
   p.max_M = s.M;
   const size_t cbytes = (size_t)s.M * s.N * sizeof(TC);
   void* ref = std::is_same<TC, float>::value ? (void*)dRef : (void*)dRef16;

@@ -35,7 +35,7 @@ __device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
   return r;
 }
 
-// f16x3 epilogue with one accumulator on the 2^11 scale (h3_epilogue's layout and epilogues)
+// f16x3 epilogue with one accumulator on the 2^11 scale (gemm_dev.h tile_epilogue's layout and epilogues)
 template <int EPI, int FM, int FN>
 __device__ __forceinline__ void h3p_epilogue(const GemmParams& p, float* sE,
                                              const f32x16 (&acc)[FM][FN], int row0, int col0,
@@ -74,13 +74,15 @@ __device__ __forceinline__ void h3p_epilogue(const GemmParams& p, float* sE,
         const int row = row0 + i * 32 + rl;
         float4 v = *reinterpret_cast<const float4*>(&sE[rl * LDE + 4 * c4]);
         if (row < M && col < N) {
-          v.x = x3_act<EPI>(v.x + bias.x);
-          v.y = x3_act<EPI>(v.y + bias.y);
-          v.z = x3_act<EPI>(v.z + bias.z);
-          v.w = x3_act<EPI>(v.w + bias.w);
+          v.x = epi_act<EPI>(v.x + bias.x);
+          v.y = epi_act<EPI>(v.y + bias.y);
+          v.z = epi_act<EPI>(v.z + bias.z);
+          v.w = epi_act<EPI>(v.w + bias.w);
           if constexpr (EPI == EPI_RESADD) {
             v.x += side[q].x; v.y += side[q].y; v.z += side[q].z; v.w += side[q].w;
-            x3_bypass(p, v, row, col);
+            if (p.byp_orig != nullptr)
+              bypass_mix(v, *reinterpret_cast<const float4*>(p.byp_orig + (long)row * p.ldc + col),
+                         *reinterpret_cast<const float4*>(p.byp_scale + col));
           }
           if constexpr (EPI == EPI_MULAUX) {
             v.x *= side[q].x; v.y *= side[q].y; v.z *= side[q].z; v.w *= side[q].w;
@@ -351,7 +353,6 @@ int main(int argc, char** argv) {
     p.M = s.M;
     p.N = s.N;
     p.K = s.K;
-    p.alpha = 1.f;
     p.max_M = s.M;
     std::mt19937 r2(11);
     std::vector<long> sm(512), sn(512);

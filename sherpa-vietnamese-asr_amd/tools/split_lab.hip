@@ -71,7 +71,6 @@ int main(int argc, char** argv) {
     p.M = s.M;
     p.N = s.N;
     p.K = s.K;
-    p.alpha = 1.f;
     p.max_M = s.M;
     // f16x3 tile variants (all bit-identical: same 16-deep slabs in the same MFMA order
     // per output; BK = 32 changes nothing in the per-output order either)

@@ -66,7 +66,6 @@ struct Lab {
     p.M = s.M;
     p.N = s.N;
     p.K = s.K;
-    p.alpha = 1.f;
     p.max_M = s.M;
     return p;
   }

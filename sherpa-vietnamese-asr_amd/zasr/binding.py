@@ -37,7 +37,7 @@ EXPORTS = (
     "zasr_fbank_set_mel_banks", "zasr_selftest_launch", "zasr_decode_host_batches",
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
-    "zasr_selftest_ffn_h3_oop",
+    "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -222,6 +222,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_launch.restype = C.c_int
     lib.zasr_selftest_gemm_h3r.argtypes = [I32, I32, I32, I32, fp, fp, fp, fp]
     lib.zasr_selftest_gemm_h3r.restype = C.c_int
+    lib.zasr_selftest_gemm.argtypes = [I32] * 7 + [fp] * 7
+    lib.zasr_selftest_gemm.restype = C.c_int
     lib.zasr_selftest_ffn_h3.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, fp]
     lib.zasr_selftest_ffn_h3.restype = C.c_int
     lib.zasr_selftest_ffn_bf16.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, I32]
@@ -321,6 +323,22 @@ def selftest_gemm_h3r(A, W, bias, C, epi: int = 0, lib_path: Optional[str] = Non
     p = lambda x: None if x is None else x.ctypes.data_as(C_FP)
     rc = lib.zasr_selftest_gemm_h3r(A.shape[0], A.shape[1], W.shape[0], int(epi), p(A), p(W),
                                     p(b), p(C))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return C
+
+
+def selftest_gemm(mode: str, A, W, bias, C, epi: int = 0, a_bf16: bool = False,
+                  c_bf16: bool = False, aux=None, byp_orig=None, byp_scale=None,
+                  lib_path: Optional[str] = None) -> np.ndarray:
+    """gemm_f32 / gemm_bf16 / gemm_x3 alone on one dense host problem (zasr_selftest_gemm;
+    mode: a PRECISIONS name): returns C after C = epi(A W^T + bias) as float32."""
+    lib = load_library(lib_path)
+    A, W, C = _f32(A), _f32(W), _f32(C).copy()
+    opt = [None if x is None else _f32(x) for x in (bias, aux, byp_orig, byp_scale)]
+    p = lambda x: None if x is None else x.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_gemm(PRECISIONS[mode], A.shape[0], A.shape[1], W.shape[0], int(epi),
+                                int(a_bf16), int(c_bf16), p(A), p(W), *(p(x) for x in opt), p(C))
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return C
