@@ -459,6 +459,43 @@ int zasr_selftest_seam(int32_t nseq, const int32_t* L, int32_t d, int32_t ds, in
                        const float* orig, const float* s, const float* wn8, const float* wo2,
                        float* next, float* xnext, float* out, float* next_ref, float* xnext_ref,
                        float* out_ref);
+/* The convolution path's hand-written kernels and BiasNorm alone on host operands (same
+   conventions; no reference counterpart: test infrastructure).  Ragged batches are given as
+   per-sequence lengths; the offsets and row -> sequence maps are built as a decode builds them,
+   and every entry makes exactly the launch call a decode makes.  Every output holds its
+   buffer's initial contents on entry and the kernel's on return; one guard row follows each
+   output on the device, and a changed guard byte returns ZASR_ERR_RUNTIME.  "bf16" operands are
+   rounded to nearest even on upload and widened on return.
+   dwconv1d: the ConvolutionModule core, out[rows][d] = SwooshR(b[c] + sum_k w[c][k] g[t + k -
+   K / 2][c]) with zero padding per sequence, rows = sum L, d % 4 == 0, K odd <= 31, w [d][K].
+   glu = 1: x [rows][2 d] and g = x[:, :d] sigmoid(x[:, d:]) (the fp32 mode); glu = 0: g = x
+   [rows][d], in f32 or (bf16 = 1) with bf16 x and out (the bf16 modes); glu with bf16 is
+   refused.
+   conv1: conv.0 (1 -> 8, 3x3, padding (0, 1)) + SwooshR, fb [sum T][80] -> out [sum (T - 2)]
+   [80][8], every T >= 3, w [8][9]; form 0 the libm SwooshR, 1 the native-exp form, 2 that form
+   with bf16 out.
+   convnext: x [rows][19][128], depthwise dw_w [128][7][7] (time, freq) + dw_b, pw1 w1 [384][128]
+   + b1, pw2 w2 [128][384] + b2.  form 0: the f32 depthwise 7x7 alone, y = dwconv(x) + dw_b (the
+   MLP's operands and out may be null).  form 1: the bf16 block, y the depthwise output and
+   out = x + pw2(SwooshL(pw1(y) + b1)) + b2, x / y / out and the pw weights in bf16.  form 2:
+   the f16x3 pair, the f32 depthwise then the fp16-piece MLP in place over x's buffer as a
+   decode runs it (out returns that buffer; its initial contents are x, not the caller's out).
+   bias_norm: x[rows][d] *= exp(log_scale) / sqrt(mean((x - bias)^2)), then, with orig and
+   bscale [d] (both or neither), x = orig + (x - orig) bscale; d % 4 == 0, d <= 1024.
+   copy_mode 0: no copy; 1: the result also to copy_out; 2: the result also over orig's own
+   device buffer (a layer's copy for the next one).  orig returns what its buffer holds
+   afterwards. */
+int zasr_selftest_dwconv1d(int32_t nseq, const int32_t* L, int32_t d, int32_t K, int32_t glu,
+                           int32_t bf16, const float* x, const float* w, const float* b,
+                           float* out);
+int zasr_selftest_conv1(int32_t nseq, const int32_t* T, int32_t form, const float* fb,
+                        const float* w, const float* b, float* out);
+int zasr_selftest_convnext(int32_t nseq, const int32_t* L, int32_t form, const float* x,
+                           const float* dw_w, const float* dw_b, const float* w1, const float* b1,
+                           const float* w2, const float* b2, float* y, float* out);
+int zasr_selftest_bias_norm(int32_t rows, int32_t d, const float* bias, float log_scale,
+                            float* orig, const float* bscale, int32_t copy_mode, float* x,
+                            float* copy_out);
 /* The attention kernels' block map alone (host only, no device call; no reference counterpart:
    test infrastructure).  lens[nseq] frames per sequence, units_per_seq heads or z-chunks;
    out[b] for block id b = sequence << 12 | unit << 8 | query tile (128 frames), or 0xffffffff

@@ -728,13 +728,6 @@ void launch_glu_dwconv1d(const float* x2, const int* off, const int* map, int to
   launch_glu_dwconv1d_t(x2, off, map, total_rows, d, K, w, b, out, st);
 }
 
-void launch_glu_dwconv1d_bf16(const void* x2, const int* off, const int* map, int total_rows,
-                              int d, int K, const float* w, const float* b, void* out,
-                              hipStream_t st) {
-  launch_glu_dwconv1d_t(reinterpret_cast<const __bf16*>(x2), off, map, total_rows, d, K, w, b,
-                        reinterpret_cast<__bf16*>(out), st);
-}
-
 // =====================================================================================
 // SimpleDownsample / SimpleUpsample + bypass, convert_num_channels
 // =====================================================================================

@@ -181,16 +181,13 @@ void Engine::conv_module(const StackCtx& c, const DLayer& Ly, int k, float* X) {
     else
       launch_dwconv1d_post_glu(reinterpret_cast<float*>(g), c.off, c.map, R, d, K, Ly.cv_dw_w[k],
                                Ly.cv_dw_b[k], reinterpret_cast<float*>(dc), st_);
-  } else {
-    void* g2 = h16 ? (void*)ws<__bf16>("ly_g2_h", 2 * n) : (void*)ws<float>("ly_g2", 2 * n);
-    project(in, X, false, d, R, g2, h16, 2 * d, EPI_NONE);
+  } else {  // fp32 only (the loader interleaves the in_proj for every other mode): f32 throughout
+    ZASR_REQUIRE(!h16, "conv module: a bf16 in_proj carries the GLU epilogue");
+    float* g2 = ws<float>("ly_g2", 2 * n);
+    project(in, X, false, d, R, g2, false, 2 * d, EPI_NONE);
     prof_begin("dwconv1d");
-    if (h16)
-      launch_glu_dwconv1d_bf16(reinterpret_cast<__bf16*>(g2), c.off, c.map, R, d, K,
-                               Ly.cv_dw_w[k], Ly.cv_dw_b[k], reinterpret_cast<__bf16*>(dc), st_);
-    else
-      launch_glu_dwconv1d(reinterpret_cast<float*>(g2), c.off, c.map, R, d, K, Ly.cv_dw_w[k],
-                          Ly.cv_dw_b[k], reinterpret_cast<float*>(dc), st_);
+    launch_glu_dwconv1d(g2, c.off, c.map, R, d, K, Ly.cv_dw_w[k], Ly.cv_dw_b[k],
+                        reinterpret_cast<float*>(dc), st_);
   }
   prof_end();
   project(Ly.cv_out[k], dc, h16, d, R, X, false, d, EPI_RESADD);

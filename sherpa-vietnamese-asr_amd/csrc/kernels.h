@@ -191,21 +191,18 @@ void launch_bypass(float* x, const float* orig, const float* s, long rows, int d
 // g[r][c] = x2[r][c] * sigmoid(x2[r][d + c])
 void launch_glu(const float* x2, float* g, long rows, int d, hipStream_t st);
 // g = x2[:, :d] * sigmoid(x2[:, d:]);  out[t][c] = SwooshR(b[c] + sum_k w[c][k] g[t+k-K/2][c]),
-// zero padding per sequence
+// zero padding per sequence (fp32 mode: x2 [rows][2 d] is the in_proj output)
+void launch_glu_dwconv1d(const float* x2, const int* off, const int* map, int total_rows, int d,
+                         int K, const float* w, const float* b, float* out, hipStream_t st);
 // the same depthwise conv + bias + SwooshR on an input that is already the GLU output
-// ([rows][d], split modes: EPI_GLU in the in_proj GEMM)
+// ([rows][d]: EPI_GLU in the in_proj GEMM, every mode but fp32); _bf16: bf16 in (the conv
+// in_proj output) / bf16 out (the conv out_proj input), the bf16 modes
 void launch_dwconv1d_post_glu(const float* g, const int* off, const int* map, int total_rows,
                               int d, int K, const float* w, const float* b, float* out,
                               hipStream_t st);
 void launch_dwconv1d_post_glu_bf16(const void* g, const int* off, const int* map,
                                    int total_rows, int d, int K, const float* w, const float* b,
                                    void* out, hipStream_t st);
-void launch_glu_dwconv1d(const float* x2, const int* off, const int* map, int total_rows, int d,
-                         int K, const float* w, const float* b, float* out, hipStream_t st);
-// bf16 in (the conv in_proj output) / bf16 out (the conv out_proj input), bf16 mode
-void launch_glu_dwconv1d_bf16(const void* x2, const int* off, const int* map, int total_rows,
-                              int d, int K, const float* w, const float* b, void* out,
-                              hipStream_t st);
 // t1[r][c] = tanh(h3[r][c]) * h3[r][hid + c]
 void launch_nonlin_prep(const float* h3, float* t1, long rows, int hid, hipStream_t st);
 // SimpleDownsample: out[t'] = sum_u w[u] x[min(ds t' + u, L - 1)]
@@ -251,6 +248,18 @@ struct SeamDesc {
   int ldo = 0, c0 = 0;
 };
 void launch_seam(const SeamDesc& s, hipStream_t st);
+// the convolution path's kernels and BiasNorm alone on host operands (selftest.cpp;
+// zasr_selftest_dwconv1d / _conv1 / _convnext / _bias_norm): offsets and row maps built from the
+// per-sequence lengths as the engine builds them, one guard row behind every output
+void selftest_dwconv1d(int nseq, const int* L, int d, int K, bool glu, bool bf16, const float* x,
+                       const float* w, const float* b, float* out);
+void selftest_conv1(int nseq, const int* T, int form, const float* fb, const float* w,
+                    const float* b, float* out);
+void selftest_convnext(int nseq, const int* L, int form, const float* x, const float* dw_w,
+                       const float* dw_b, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* y, float* out);
+void selftest_bias_norm(int rows, int d, const float* bias, float log_scale, float* orig,
+                        const float* bscale, int copy_mode, float* x, float* copy_out);
 // row -> sequence index map for one resolution (off: [nseq + 1])
 void launch_row2seq(const int* off, int nseq, int total, int* map, hipStream_t st);
 // dst[r][0:dd] = src[r][0:min(ds, dd)], zero-padded  (convert_num_channels)

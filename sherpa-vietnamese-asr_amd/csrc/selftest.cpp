@@ -2,9 +2,10 @@
 // points, the f16x3 one-accumulator kernels and the bf16 fused FFN run alone on caller-supplied
 // operands, so the tests can sweep the shapes and row counts the decode only reaches
 // incidentally (tail tiles, M < 16, every K / D and epilogue) against a float64 product on the
-// host; the fused FFNs also out of place, and the fused stack seam beside the kernels it
-// replaces.  Device 0 of the process, its null stream, synchronous; nothing here is on the
-// decode path.
+// host; the fused FFNs also out of place, the fused stack seam beside the kernels it
+// replaces, and the convolution path's hand-written kernels (ConvolutionModule depthwise conv,
+// conv.0, the ConvNeXt block) and BiasNorm on ragged batches given as per-sequence lengths.
+// Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -299,6 +300,206 @@ void selftest_seam(int nseq, const int* L, int d, int ds, int dn, int ds_next, i
   }
   down(out, dout, bout);
   down(out_ref, dout_r, bout);
+}
+
+// ---- the convolution path's kernels and BiasNorm ----
+namespace {
+std::vector<__bf16> round16(const float* s, size_t n) {
+  std::vector<__bf16> h(n);
+  for (size_t i = 0; i < n; ++i) h[i] = (__bf16)s[i];
+  return h;
+}
+
+// one ragged level as the engine forms it: offsets from the per-sequence lengths (each less
+// `cut` frames), the row -> sequence map from launch_row2seq
+struct Level {
+  std::vector<int> off;
+  int rows;
+  DevBuf d_off, d_map;
+  Level(int nseq, const int* len, int cut)
+      : off(offsets(nseq, len, cut)), rows(off.back()), d_off(off.size() * 4),
+        d_map((size_t)rows * 4) {
+    up(d_off, off.data(), off.size() * 4);
+    launch_row2seq(d_off.as<int>(), nseq, rows, d_map.as<int>(), nullptr);
+  }
+  static std::vector<int> offsets(int nseq, const int* len, int cut) {
+    ZASR_REQUIRE(nseq >= 1 && len != nullptr, "selftest: at least one sequence");
+    std::vector<int> o(nseq + 1, 0);
+    for (int b = 0; b < nseq; ++b) {
+      ZASR_REQUIRE(len[b] - cut >= 1, "selftest: every sequence needs a frame at every level");
+      o[b + 1] = o[b] + len[b] - cut;
+    }
+    return o;
+  }
+};
+
+// an output image of n elements (f32, or bf16: rounded to nearest even on upload, widened on
+// return) that starts as the caller's, with one guard row of `row` elements behind it
+struct OutBuf {
+  size_t n, row, eb;
+  DevBuf d;
+  OutBuf(const float* init, size_t n_, size_t row_, bool h16)
+      : n(n_), row(row_), eb(h16 ? 2 : 4), d((n_ + row_) * (h16 ? 2 : 4)) {
+    if (h16) up(d, round16(init, n).data(), n * 2);
+    else up(d, init, n * 4);
+    ZASR_HIP_CHECK(hipMemset(d.as<unsigned char>() + n * eb, 0x5a, row * eb));
+  }
+  template <class T>
+  T* as() const { return d.as<T>(); }
+  // after the kernel: the guard row intact, then the image back to the caller
+  void down(float* out, const char* what) const {
+    std::vector<unsigned char> guard(row * eb);
+    ZASR_HIP_CHECK(hipMemcpy(guard.data(), d.as<unsigned char>() + n * eb, guard.size(),
+                             hipMemcpyDeviceToHost));
+    for (unsigned char g : guard)
+      ZASR_REQUIRE(g == 0x5a, std::string("selftest ") + what + ": the kernel wrote past the last row");
+    if (n == 0) return;
+    if (eb == 2) {
+      std::vector<__bf16> h(n);
+      ZASR_HIP_CHECK(hipMemcpy(h.data(), d.p, n * 2, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
+    } else {
+      ZASR_HIP_CHECK(hipMemcpy(out, d.p, n * 4, hipMemcpyDeviceToHost));
+    }
+  }
+};
+
+void up16(DevBuf& d, const float* h, size_t n, bool h16) {
+  if (h16) up(d, round16(h, n).data(), n * 2);
+  else up(d, h, n * 4);
+}
+}  // namespace
+
+void selftest_dwconv1d(int nseq, const int* L, int d, int K, bool glu, bool bf16, const float* x,
+                       const float* w, const float* b, float* out) {
+  ZASR_REQUIRE(!(glu && bf16), "selftest dwconv1d: the GLU form is f32 only");
+  ZASR_REQUIRE(d >= 4 && d % 4 == 0, "selftest dwconv1d: d a positive multiple of 4");
+  ZASR_REQUIRE(K >= 1 && K <= 31 && (K & 1), "selftest dwconv1d: K odd, at most 31");
+  Level lv(nseq, L, 0);
+  const size_t nx = (size_t)lv.rows * (glu ? 2 * d : d), no = (size_t)lv.rows * d;
+  DevBuf dX(nx * (bf16 ? 2 : 4)), dW((size_t)d * K * 4), dB((size_t)d * 4);
+  up16(dX, x, nx, bf16);
+  up(dW, w, (size_t)d * K * 4);
+  up(dB, b, (size_t)d * 4);
+  OutBuf o(out, no, d, bf16);
+  if (glu)
+    launch_glu_dwconv1d(dX.as<float>(), lv.d_off.as<int>(), lv.d_map.as<int>(), lv.rows, d, K,
+                        dW.as<float>(), dB.as<float>(), o.as<float>(), nullptr);
+  else if (bf16)
+    launch_dwconv1d_post_glu_bf16(dX.p, lv.d_off.as<int>(), lv.d_map.as<int>(), lv.rows, d, K,
+                                  dW.as<float>(), dB.as<float>(), o.d.p, nullptr);
+  else
+    launch_dwconv1d_post_glu(dX.as<float>(), lv.d_off.as<int>(), lv.d_map.as<int>(), lv.rows, d, K,
+                             dW.as<float>(), dB.as<float>(), o.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(out, "dwconv1d");
+}
+
+void selftest_conv1(int nseq, const int* T, int form, const float* fb, const float* w,
+                    const float* b, float* out) {
+  ZASR_REQUIRE(form >= 0 && form <= 2, "selftest conv1: form 0 (libm), 1 (fast) or 2 (bf16 out)");
+  Level lf(nseq, T, 0), lc(nseq, T, 2);  // fbank rows, conv.0 rows (T - 2 per sequence)
+  DevBuf dF((size_t)lf.rows * 80 * 4), dW(8 * 9 * 4), dB(8 * 4);
+  up(dF, fb, (size_t)lf.rows * 80 * 4);
+  up(dW, w, 8 * 9 * 4);
+  up(dB, b, 8 * 4);
+  OutBuf o(out, (size_t)lc.rows * 640, 640, form == 2);
+  launch_conv1(dF.as<float>(), lf.d_off.as<int>(), lc.d_off.as<int>(), lc.d_map.as<int>(), lc.rows,
+               dW.as<float>(), dB.as<float>(), o.d.p, form == 2, nullptr, form == 1);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(out, "conv1");
+}
+
+void selftest_convnext(int nseq, const int* L, int form, const float* x, const float* dw_w,
+                       const float* dw_b, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* y, float* out) {
+  ZASR_REQUIRE(form >= 0 && form <= 2,
+               "selftest convnext: form 0 (depthwise f32), 1 (bf16 block) or 2 (f16x3 block)");
+  ZASR_REQUIRE(form == 0 || (w1 && b1 && w2 && b2 && out), "selftest convnext: the MLP's operands");
+  Level lv(nseq, L, 0);
+  constexpr size_t kRow = 19 * 128, kW = 384 * 128;
+  const size_t n = (size_t)lv.rows * kRow;
+  const bool h16 = form == 1;
+  DevBuf dWd(128 * 49 * 4), dBd(128 * 4), d1(2 * kW * 2), d2(2 * kW * 2), db1(384 * 4), db2(128 * 4);
+  up(dWd, dw_w, 128 * 49 * 4);
+  up(dBd, dw_b, 128 * 4);
+  OutBuf oy(y, n, kRow, h16);
+  const int *off = lv.d_off.as<int>(), *map = lv.d_map.as<int>();
+  if (form == 0) {
+    DevBuf dX(n * 4);
+    up(dX, x, n * 4);
+    launch_dwconv2d_tiled(dX.as<float>(), off, map, lv.rows, dWd.as<float>(), dBd.as<float>(),
+                          oy.as<float>(), nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    oy.down(y, "convnext");
+    return;
+  }
+  up(db1, b1, 384 * 4);
+  up(db2, b2, 128 * 4);
+  // pw1 [384][128] / pw2 [128][384] as the loader prepares them (engine_load.cpp): bf16, or the
+  // two fp16 pieces (hi, (w - hi) * 2^11), every image in MFMA-fragment order
+  auto pack = [&](const float* wsrc, int rows, int cols, DevBuf& dst) {
+    std::vector<__bf16> img(2 * kW), piece(kW);
+    if (h16) {
+      pack_frag32_host(round16(wsrc, kW).data(), rows, cols, img.data());
+    } else {
+      for (int t = 0; t < 2; ++t) {
+        for (size_t i = 0; i < kW; ++i) {
+          const _Float16 hi = (_Float16)wsrc[i];
+          const _Float16 v = t == 0 ? hi : (_Float16)((wsrc[i] - (float)hi) * 2048.f);
+          std::memcpy(&piece[i], &v, 2);
+        }
+        pack_frag32_host(piece.data(), rows, cols, img.data() + t * kW);
+      }
+    }
+    up(dst, img.data(), (h16 ? 1 : 2) * kW * 2);
+  };
+  pack(w1, 384, 128, d1);
+  pack(w2, 128, 384, d2);
+  if (h16) {
+    DevBuf dX(n * 2);
+    up16(dX, x, n, true);
+    OutBuf oo(out, n, kRow, true);
+    launch_convnext_bf16(dX.p, off, map, lv.rows, dWd.as<float>(), dBd.as<float>(), d1.p,
+                         db1.as<float>(), d2.p, db2.as<float>(), oy.d.p, oo.d.p, nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    oy.down(y, "convnext");
+    oo.down(out, "convnext");
+    return;
+  }
+  // f16x3: the engine's pair of calls, the MLP in place over x (its residual and its output)
+  OutBuf ox(x, n, kRow, false);
+  launch_dwconv2d_tiled(ox.as<float>(), off, map, lv.rows, dWd.as<float>(), dBd.as<float>(),
+                        oy.as<float>(), nullptr);
+  launch_convnext_mlp_h3(oy.as<float>(), ox.as<float>(), (long)lv.rows * 19, d1.p, db1.as<float>(),
+                         d2.p, db2.as<float>(), ox.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  oy.down(y, "convnext");
+  ox.down(out, "convnext");
+}
+
+void selftest_bias_norm(int rows, int d, const float* bias, float log_scale, float* orig,
+                        const float* bscale, int copy_mode, float* x, float* copy_out) {
+  ZASR_REQUIRE(rows >= 1 && d >= 4, "selftest bias_norm: rows >= 1, d >= 4");
+  ZASR_REQUIRE((orig == nullptr) == (bscale == nullptr), "selftest bias_norm: the blend takes both operands");
+  ZASR_REQUIRE(copy_mode >= 0 && copy_mode <= 2 && (copy_mode != 1 || copy_out != nullptr) &&
+                   (copy_mode != 2 || orig != nullptr),
+               "selftest bias_norm: copy_mode 0 (none), 1 (copy_out) or 2 (over orig)");
+  const size_t n = (size_t)rows * d;
+  DevBuf dB((size_t)d * 4), dS((size_t)d * 4);
+  up(dB, bias, (size_t)d * 4);
+  if (bscale) up(dS, bscale, (size_t)d * 4);
+  OutBuf ox(x, n, d, false);
+  std::unique_ptr<OutBuf> oo, oc;
+  if (orig) oo.reset(new OutBuf(orig, n, d, false));
+  if (copy_mode == 1) oc.reset(new OutBuf(copy_out, n, d, false));
+  float* co = copy_mode == 1 ? oc->as<float>() : copy_mode == 2 ? oo->as<float>() : nullptr;
+  launch_bias_norm(ox.as<float>(), rows, d, dB.as<float>(), log_scale,
+                   orig ? oo->as<float>() : nullptr, bscale ? dS.as<float>() : nullptr, nullptr, co);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  ox.down(x, "bias_norm");
+  if (oo) oo->down(orig, "bias_norm");
+  if (oc) oc->down(copy_out, "bias_norm");
 }
 
 }  // namespace zasr

@@ -751,6 +751,45 @@ int zasr_selftest_seam(int32_t nseq, const int32_t* L, int32_t d, int32_t ds, in
   });
 }
 
+int zasr_selftest_dwconv1d(int32_t nseq, const int32_t* L, int32_t d, int32_t K, int32_t glu,
+                           int32_t bf16, const float* x, const float* w, const float* b,
+                           float* out) {
+  if (!L || !x || !w || !b || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_dwconv1d(nseq, L, d, K, glu != 0, bf16 != 0, x, w, b, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_conv1(int32_t nseq, const int32_t* T, int32_t form, const float* fb,
+                        const float* w, const float* b, float* out) {
+  if (!T || !fb || !w || !b || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_conv1(nseq, T, form, fb, w, b, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_convnext(int32_t nseq, const int32_t* L, int32_t form, const float* x,
+                           const float* dw_w, const float* dw_b, const float* w1, const float* b1,
+                           const float* w2, const float* b2, float* y, float* out) {
+  if (!L || !x || !dw_w || !dw_b || !y) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_convnext(nseq, L, form, x, dw_w, dw_b, w1, b1, w2, b2, y, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_bias_norm(int32_t rows, int32_t d, const float* bias, float log_scale,
+                            float* orig, const float* bscale, int32_t copy_mode, float* x,
+                            float* copy_out) {
+  if (!bias || !x) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_bias_norm(rows, d, bias, log_scale, orig, bscale, copy_mode, x, copy_out);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
                                  int32_t order, uint32_t* out, int64_t cap, int32_t* grid) {
   if (!lens || !grid || (cap > 0 && !out) || cap < 0) return fail(ZASR_ERR_INVALID, "null argument");

@@ -38,6 +38,8 @@ EXPORTS = (
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
     "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm",
+    "zasr_selftest_dwconv1d", "zasr_selftest_conv1", "zasr_selftest_convnext",
+    "zasr_selftest_bias_norm",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -237,6 +239,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_ffn_bf16_oop.restype = C.c_int
     lib.zasr_selftest_ffn_h3_oop.argtypes = [I32, I32, I32] + [fp] * 8
     lib.zasr_selftest_ffn_h3_oop.restype = C.c_int
+    lib.zasr_selftest_dwconv1d.argtypes = [I32, C.POINTER(I32)] + [I32] * 4 + [fp] * 4
+    lib.zasr_selftest_dwconv1d.restype = C.c_int
+    lib.zasr_selftest_conv1.argtypes = [I32, C.POINTER(I32), I32] + [fp] * 4
+    lib.zasr_selftest_conv1.restype = C.c_int
+    lib.zasr_selftest_convnext.argtypes = [I32, C.POINTER(I32), I32] + [fp] * 9
+    lib.zasr_selftest_convnext.restype = C.c_int
+    lib.zasr_selftest_bias_norm.argtypes = [I32, I32, fp, C.c_float, fp, fp, I32, fp, fp]
+    lib.zasr_selftest_bias_norm.restype = C.c_int
     # device audio front end (zasr/audio.py)
     lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
     lib.zasr_audio_create.restype = C.c_int
@@ -452,6 +462,89 @@ def selftest_seam(L, d: int, ds: int, dn: int, ds_next: int, c0: int, ldo: int, 
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return res
+
+
+def _lens(L) -> np.ndarray:
+    return np.ascontiguousarray(L, dtype=np.int32)
+
+
+def selftest_dwconv1d(L, x, w, b, glu: bool, bf16: bool = False, fill: float = -777.25,
+                      lib_path: Optional[str] = None) -> np.ndarray:
+    """The ConvolutionModule's depthwise kernel alone on a ragged batch of len(L) sequences
+    (zasr_selftest_dwconv1d): x [sum L][2 d] (glu) or [sum L][d], w [d][K], b [d]; returns
+    out [sum L][d], which started as `fill`.  bf16: x rounded to bf16, out widened."""
+    lib = load_library(lib_path)
+    L, x, w, b = _lens(L), _f32(x), _f32(w), _f32(b)
+    rows, (d, K) = int(L.sum()), w.shape
+    assert x.shape == (rows, 2 * d if glu else d) and b.shape == (d,)
+    out = np.full((rows, d), fill, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_dwconv1d(len(L), L.ctypes.data_as(C.POINTER(C.c_int32)), d, K,
+                                    int(glu), int(bf16), p(x), p(w), p(b), p(out))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out
+
+
+def selftest_conv1(T, fb, w, b, form: int, fill: float = -777.25,
+                   lib_path: Optional[str] = None) -> np.ndarray:
+    """conv.0 + SwooshR alone (zasr_selftest_conv1): fb [sum T][80], w [8][9], b [8]; returns
+    out [sum (T - 2)][80][8], which started as `fill`.  form 0: libm SwooshR, 1: the native
+    form, 2: the native form with bf16 out."""
+    lib = load_library(lib_path)
+    T, fb, w, b = _lens(T), _f32(fb), _f32(w), _f32(b)
+    assert fb.shape == (int(T.sum()), 80) and w.shape == (8, 9) and b.shape == (8,)
+    out = np.full((int((T - 2).sum()), 80, 8), fill, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_conv1(len(T), T.ctypes.data_as(C.POINTER(C.c_int32)), int(form), p(fb),
+                                 p(w), p(b), p(out))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out
+
+
+def selftest_convnext(L, x, dw_w, dw_b, w1=None, b1=None, w2=None, b2=None, form: int = 0,
+                      fill: float = -777.25, lib_path: Optional[str] = None):
+    """The ConvNeXt block's kernels alone (zasr_selftest_convnext): x [sum L][19][128], dw_w
+    [128][7][7], dw_b [128], w1 [384][128], b1 [384], w2 [128][384], b2 [128].  Returns
+    (y, out): the depthwise output and the block output (form 0: out is None), both started as
+    `fill` (form 2 runs the MLP in place over x's buffer, as a decode does).  form 0: the f32
+    depthwise kernel, 1: the bf16 pair, 2: the f32 depthwise kernel + the f16x3 MLP."""
+    lib = load_library(lib_path)
+    L, x, dw_w, dw_b = _lens(L), _f32(x), _f32(dw_w), _f32(dw_b)
+    rows = int(L.sum())
+    assert x.shape == (rows, 19, 128) and dw_w.shape == (128, 7, 7) and dw_b.shape == (128,)
+    mlp = [None if v is None else _f32(v) for v in (w1, b1, w2, b2)]
+    if form != 0:
+        assert [v.shape for v in mlp] == [(384, 128), (384,), (128, 384), (128,)]
+    y = np.full(x.shape, fill, dtype=np.float32)
+    out = None if form == 0 else np.full(x.shape, fill, dtype=np.float32)
+    p = lambda a: None if a is None else a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_convnext(len(L), L.ctypes.data_as(C.POINTER(C.c_int32)), int(form),
+                                    p(x), p(dw_w), p(dw_b), *(p(v) for v in mlp), p(y), p(out))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return y, out
+
+
+def selftest_bias_norm(x, bias, log_scale: float, orig=None, bscale=None, copy_mode: int = 0,
+                       fill: float = -777.25, lib_path: Optional[str] = None) -> dict:
+    """bias_norm_kernel alone (zasr_selftest_bias_norm): x [rows][d], bias [d], optionally the
+    bypass blend with orig [rows][d] and bscale [d].  copy_mode 1: the result also to a second
+    buffer (which started as `fill`), 2: also over orig's own device buffer.  Returns {"x",
+    "orig" (what its buffer holds afterwards, or None), "copy" (copy_mode 1, else None)}."""
+    lib = load_library(lib_path)
+    x, bias = _f32(x).copy(), _f32(bias)
+    rows, d = x.shape
+    o = None if orig is None else _f32(orig).copy()
+    s = None if bscale is None else _f32(bscale)
+    cp = np.full(x.shape, fill, dtype=np.float32) if copy_mode == 1 else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_bias_norm(rows, d, p(bias), float(log_scale), p(o), p(s),
+                                     int(copy_mode), p(x), p(cp))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return {"x": x, "orig": o, "copy": cp}
 
 
 def silence_flags(d_wav_ptr: int, n: int, frame_len: int, threshold: float, d_flags_ptr: int,
