@@ -425,6 +425,23 @@ int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const 
 int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t epi, int32_t a_bf16,
                        int32_t c_bf16, const float* A, const float* W, const float* bias,
                        const float* aux, const float* byp_orig, const float* byp_scale, float* C);
+/* The joiner kernels alone on one host problem (same conventions): out[M][V] = J[M][D]
+   W[V][D]^T + bias through the launcher a decode uses.  mode: ZASR_PRECISION_FP32, _BF16,
+   _BF16X3, _BF16X6 or _F16X3.  layout 0: row-major J (f32; rounded to bf16 on upload in the bf16
+   mode), the 32 x 32 split-K kernels, D in {64, 128, 256, 512}.  layout 1: J and W in
+   MFMA-fragment order (the speculative-greedy / beam joiner; every mode but fp32, D = 256 or
+   512): J is laid out on the host as the search kernels write it (rows padded to a multiple of
+   64, the pad rows finite and non-zero; the split modes' bf16 / fp16 pieces one image each).  W
+   is prepared as the model loader prepares the joiner weight.  live_t / live_len
+   [ceil(M / live_f)] and live_f: the finished-stream filter of the greedy windows (row r
+   belongs to stream r / live_f; a tile whose streams all have live_t >= live_len may be
+   skipped), or null / 0 for every row.  out holds the buffer's initial contents on entry, so a
+   skipped tile keeps them.  A mode / layout / D combination outside the above returns
+   ZASR_ERR_INVALID. */
+int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int32_t D,
+                         const float* J, const float* W, const float* bias,
+                         const int32_t* live_t, const int32_t* live_len, int32_t live_f,
+                         float* out);
 /* The bf16 mode's fused FeedforwardModule alone on host operands (same conventions):
    X[R][D] += W2 SwooshL(W1 bf16(X) + b1) + b2 with W1 [F][D], W2 [D][F] rounded to bf16 and
    the hidden activation in bf16 (then the bypass_mid blend when byp_orig is given);

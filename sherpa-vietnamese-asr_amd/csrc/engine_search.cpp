@@ -33,37 +33,24 @@ struct JoinerRoute {
         images(packed && pieces > 0 ? stored_pieces(pieces) : 1),
         j16(bf16 || packed) {}
 
-  JoinerPackedArgs packed_args(const void* Jp, long j_plane, float* out, int rows) const {
-    JoinerPackedArgs ja{Jp, m.joiner_packed, m.joiner.b, out, rows, m.cfg.V, m.cfg.joiner_dim};
-    if (pieces > 0) {
-      ja.pieces = pieces;
-      ja.j_plane = j_plane;
-      ja.w_plane = m.joiner_plane;
-    }
+  // out[rows][V] = joiner(J), every row (kernels.h JoinerArgs)
+  JoinerArgs args(const void* J, long j_plane, float* out, int rows) const {
+    const void* W = packed ? m.joiner_packed : bf16 ? m.joiner.wh : pieces > 0 ? m.joiner.wx : m.joiner.w;
+    JoinerArgs ja{J, W, m.joiner.b, out, rows, m.cfg.V, m.cfg.joiner_dim};
+    ja.layout = packed ? JOINER_PACKED : bf16 ? JOINER_BF16 : JOINER_F32;
+    ja.pieces = pieces;
+    ja.j_plane = j_plane;
+    ja.w_plane = packed ? m.joiner_plane : (long)m.cfg.V * m.cfg.joiner_dim;
     return ja;
   }
-  // out[rows][V] = joiner(J); live_t / live_len / live_f: the greedy windows' live-stream
-  // filter (null / 0: every row)
+  // live_t / live_len / live_f: the greedy windows' live-stream filter (null / 0: every row)
   void launch(const void* J, long j_plane, float* out, int rows, const int* live_t,
               const int* live_len, int live_f, hipStream_t st) const {
-    const int V = m.cfg.V, D = m.cfg.joiner_dim;
-    if (packed) {
-      JoinerPackedArgs ja = packed_args(J, j_plane, out, rows);
-      ja.live_t = live_t;
-      ja.live_len = live_len;
-      ja.live_f = live_f;
-      launch_joiner_packed(ja, st);
-    } else if (bf16) {
-      JoinerBf16Args ja{reinterpret_cast<const __bf16*>(J), reinterpret_cast<const __bf16*>(m.joiner.wh),
-                        m.joiner.b, out, rows, V, D, live_t, live_len, live_f};
-      launch_joiner_bf16(ja, st);
-    } else {
-      JoinerArgs ja{reinterpret_cast<const float*>(J), m.joiner.w, m.joiner.b, out, rows, V, D,
-                    live_t, live_len, live_f};
-      ja.Wx = reinterpret_cast<const __bf16*>(m.joiner.wx);
-      ja.pieces = pieces;
-      launch_joiner(ja, st);
-    }
+    JoinerArgs ja = args(J, j_plane, out, rows);
+    ja.live_t = live_t;
+    ja.live_len = live_len;
+    ja.live_f = live_f;
+    launch_joiner(ja, st);
   }
   // the decoder-context table writing the next frame's joiner input into J (jrows packed rows)
   DecTable dec_table(const float* d_enc, const int* d_eo, const int* d_el, void* J,
@@ -211,7 +198,7 @@ void Engine::launch_search(const float* d_enc, const std::vector<int>& t_out, in
       for (int b = 0; b < kSync && k < Tmax; ++b, ++k) {
         if (fused) {
           GreedyFusedArgs ga{};
-          ga.j = jr.packed_args(Js, ds.j_plane, lg, S * F);
+          ga.j = jr.args(Js, ds.j_plane, lg, S * F);
           ga.ldo = ldo;
           ga.st = st;
           ga.t_cur = d_t;

@@ -42,6 +42,11 @@ void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float
 void selftest_gemm(int mode, int M, int K, int N, int epi, bool a_bf16, bool c_bf16,
                    const float* A, const float* W, const float* bias, const float* aux,
                    const float* byp_orig, const float* byp_scale, float* C);
+// out[M][V] = J W^T + bias through the decode's joiner launcher (layout 0: row-major J; 1: J
+// packed on the host in fragment order, W by gemm_rp_pack_weights); out in / out
+void selftest_joiner(int mode, int layout, int M, int V, int D, const float* J, const float* W,
+                     const float* bias, const int* live_t, const int* live_len, int live_f,
+                     float* out);
 void selftest_ffn_h3(int R, int D, int F, const float* Y, const float* W1, const float* b1,
                      const float* W2, const float* b2, const float* byp_orig,
                      const float* byp_scale, float* X, float* Xout = nullptr);
@@ -470,27 +475,35 @@ struct DecJoinArgs {
   int M, H, t;
   int j_bf16;
 };
+// The joiner: out[M][V] = J W^T + bias, by J's layout and the `pieces` code of the split modes
+// (gemm.h; 0 otherwise).
+//   JOINER_F32     J f32 [M][D] (decjoin_kernel, store_j4).  pieces 0: W f32 [V][D].  Split
+//                  modes: W as bf16 / fp16 pieces [V][D] (split_to_bf16), piece t at W +
+//                  t w_plane; J is split as it is loaded.  32 x 32 tiles, four waves split K.
+//   JOINER_BF16    J and W bf16, row-major; the same tiles.
+//   JOINER_PACKED  J and W in MFMA-fragment order, [row or col / 32][D / 16][64 lanes][8] bf16:
+//                  element (r, k) at ((r / 32 * (D / 16) + k / 16) * 64 + r % 32 +
+//                  32 * (k / 8 % 2)) * 8 + k % 8.  J is written so by the search kernels
+//                  (store_j4; joiner_packed_rows(M) rows), W packed once at load by
+//                  gemm_rp_pack_weights (zero beyond V); D = 256 or 512.  pieces 0: one bf16
+//                  image of each.  Split modes: one image per stored piece, piece t of J at J +
+//                  t j_plane, of W at W + t w_plane (bf16 elements), and the logits are the f32
+//                  sum of the piece products.  Register-staged, no LDS: a block is 64 x 64
+//                  outputs, each of its 4 waves streaming one J row tile and one W column group
+//                  over all of D with coalesced 1 KB fragment loads, two register sets deep.
 // live_t / live_len / live_f (optional): rows are (stream, window frame) = (r / live_f,
-// r % live_f); a 32-row tile whose streams are all finished (live_t >= live_len) is skipped
+// r % live_f); a 32-row tile (JOINER_PACKED: a 64-row block) whose streams are all finished
+// (live_t >= live_len) is skipped
+enum JoinerLayout { JOINER_F32 = 0, JOINER_BF16 = 1, JOINER_PACKED = 2 };
 struct JoinerArgs {
-  const float* J;        // [M][D]
-  const float* W;        // [V][D]
+  const void* J;
+  const void* W;
   const float* bias;     // [V]
   float* out;            // [M][V]
   int M, V, D;
-  const int* live_t = nullptr;
-  const int* live_len = nullptr;
-  int live_f = 0;
-  // split-bf16 modes: W_out as `pieces` bf16 pieces (piece t at Wx + t V D); J stays f32
-  const __bf16* Wx = nullptr;
+  int layout = JOINER_F32;
   int pieces = 0;
-};
-struct JoinerBf16Args {
-  const __bf16* J;       // [M][D]
-  const __bf16* W;       // [V][D]
-  const float* bias;     // [V]
-  float* out;            // [M][V]
-  int M, V, D;
+  long j_plane = 0, w_plane = 0;
   const int* live_t = nullptr;
   const int* live_len = nullptr;
   int live_f = 0;
@@ -515,27 +528,6 @@ struct DecTable {
   int j_pieces = 0;
   long j_plane = 0;
 };
-// Speculative-greedy joiner on fragment-packed operands: J packed by the greedy search
-// kernels ([row/32][D/16][64 lanes][8] bf16, rows padded to a multiple of 64), W packed once
-// at load by gemm_rp_pack_weights ([col/32][D/16][64][8], zero beyond V).  One block per
-// 64 x 64 output tile: both 64 KB operand tiles cross into LDS once with coalesced 16-byte
-// loads (every load of the block in flight together), 4 waves x one 32 x 32 tile over all of D.
-struct JoinerPackedArgs {
-  const void* Jp;
-  const void* Wp;
-  const float* bias;   // [V]
-  float* out;          // [M][V]
-  int M, V, D;
-  const int* live_t = nullptr;
-  const int* live_len = nullptr;
-  int live_f = 0;
-  // split-bf16 modes: J and W as `pieces` packed images each (piece t of J at Jp + t j_plane,
-  // of W at Wp + t w_plane, in bf16 elements); the logits are the f32 sum of the piece
-  // products with u + v < pieces (joiner_split_packed_kernel)
-  int pieces = 0;
-  long j_plane = 0, w_plane = 0;
-};
-void launch_joiner_packed(const JoinerPackedArgs& j, hipStream_t st);
 // *flag (device int) = 1 if any of the n floats of x is not finite, else 0
 void launch_nonfinite_check(const float* x, long n, int* flag, hipStream_t st);
 // rows the packed J buffer must hold for M joiner rows
@@ -543,7 +535,6 @@ inline long joiner_packed_rows(long M) { return (M + 63) / 64 * 64; }
 void launch_search_init(const SearchState& s, int S, int Hmax, hipStream_t st);
 void launch_decjoin(const DecJoinArgs& a, hipStream_t st);
 void launch_joiner(const JoinerArgs& j, hipStream_t st);
-void launch_joiner_bf16(const JoinerBf16Args& j, hipStream_t st);
 // table[(y2 V + y1) D + n] = decoder_proj(relu(conv(E[y2], E[y1])))[n], all V^2 contexts
 void launch_dec_table(const DecoderW& dw, const float* wp, int V, float* table, hipStream_t st);
 // J of frame 0 for slot 0 of every stream (context (0, 0))
@@ -574,7 +565,7 @@ void launch_greedy_spec(const SearchState& s, const float* logits, int V, int S,
 // its boundary.  F = 4.  `out` rows have stride ldo (>= V, a multiple of 32); cnt: one int
 // per row tile, zero before the first launch (each tile's last block re-zeroes it).
 struct GreedyFusedArgs {
-  JoinerPackedArgs j;  // j.out = logits [S * 4][ldo], j.M = S * 4
+  JoinerArgs j;  // JOINER_PACKED; j.out = logits [S * 4][ldo], j.M = S * 4
   int ldo;
   SearchState st;
   int* t_cur;

@@ -135,6 +135,73 @@ __device__ __forceinline__ bool tile_done(const int* live_t, const int* live_len
   return true;
 }
 
+// a 32 x 32 MFMA accumulator + bias to out rows row0 .. row0 + 31 (below M), column col (below
+// V): lane (col, h) holds rows (r & 3) + 8 (r >> 2) + 4 h of its column
+__device__ __forceinline__ void store_tile32(const f32x16& acc, const float* bias, float* out,
+                                             int ldo, int row0, int M, int col, int V, int h) {
+  if (col >= V) return;
+  const float b = bias[col];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    if (row < M) out[(long)row * ldo + col] = acc[r] + b;
+  }
+}
+
+// acc = one 32 x 32 tile over all of D from fragment-packed operands (kernels.h JoinerArgs,
+// JOINER_PACKED): srcJ / srcW point at this lane's slot of the row tile's / column group's first
+// fragment, piece t of either jp / wp bf16x8 units on.  QK = D / 16 k16 steps, CH of them per
+// register set: the next set's loads go out as one group before this set's MFMAs.  NP = 1: bf16;
+// NP pieces, FMT 0: the NP (NP + 1) / 2 piece products smallest first (mfma_split, the order of
+// gemm_x3 / joiner_split_kernel); FMT 1: the f16x3 format (mfma_h3, hi + lo * 2^-11).  The split
+// forms fence each set with scheduling barriers: left alone, the compiler streams one load per
+// MFMA with ~4 in flight, latency-bound.
+template <int QK, int NP, int CH, int FMT>
+__device__ __forceinline__ void packed_tile_mma(const bf16x8* srcJ, const bf16x8* srcW, long jp,
+                                                long wp, f32x16& acc) {
+  constexpr int NCH = QK / CH;
+  bf16x8 a[2][CH][NP], b[2][CH][NP];
+#pragma unroll
+  for (int c = 0; c < CH; ++c)
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      a[0][c][t] = srcJ[t * jp + c * 64];
+      b[0][c][t] = srcW[t * wp + c * 64];
+    }
+  f32x16 accl;  // the lo products (FMT 1)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = accl[r] = 0.f;
+#pragma unroll
+  for (int h = 0; h < NCH; ++h) {
+    const int cur = h & 1;
+    if (h + 1 < NCH) {
+#pragma unroll
+      for (int c = 0; c < CH; ++c)
+#pragma unroll
+        for (int t = 0; t < NP; ++t) {
+          a[cur ^ 1][c][t] = srcJ[t * jp + ((h + 1) * CH + c) * 64];
+          b[cur ^ 1][c][t] = srcW[t * wp + ((h + 1) * CH + c) * 64];
+        }
+    }
+    if constexpr (NP > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      if constexpr (FMT == 1) {
+        const bf16x8 x[2] = {a[cur][c][0], a[cur][c][1]};
+        const bf16x8 y[2] = {b[cur][c][0], b[cur][c][1]};
+        mfma_h3(x, y, acc, accl);
+      } else {
+        acc = mfma_split<NP>(a[cur][c], b[cur][c], acc);
+      }
+    }
+    if constexpr (NP > 1) __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (FMT == 1) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] += accl[r] * kF16LoInv;
+  }
+}
+
 // ---- wave reductions on DPP + readlane (no LDS round trips) ----
 // The search kernels run one block per stream, one wave per SIMD: every cross-lane step is
 // exposed latency.  __shfl_xor lowers to ds_bpermute_b32 (an LDS round trip per step, six per
@@ -372,6 +439,8 @@ __global__ __launch_bounds__(256) void joiner_kernel(JoinerArgs j) {
   const int lda = D + 4;
   float* As = smem;
   float* red = smem + 32 * lda;
+  const float* J = reinterpret_cast<const float*>(j.J);
+  const float* W = reinterpret_cast<const float*>(j.W);
   const int m0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
   if (tile_done(j.live_t, j.live_len, j.live_f, m0, j.M)) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -380,7 +449,7 @@ __global__ __launch_bounds__(256) void joiner_kernel(JoinerArgs j) {
     const int i = e / d4, k4 = e - i * d4;
     const int r = m0 + i;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < j.M) v = reinterpret_cast<const float4*>(j.J + (long)r * D)[k4];
+    if (r < j.M) v = reinterpret_cast<const float4*>(J + (long)r * D)[k4];
     *reinterpret_cast<float4*>(As + i * lda + 4 * k4) = v;
   }
   __syncthreads();
@@ -389,44 +458,9 @@ __global__ __launch_bounds__(256) void joiner_kernel(JoinerArgs j) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  tile32_splitk<NQ>(As, lda, j.W + (long)(nv ? n : 0) * D, nv, wid * (D / 4), acc);
+  tile32_splitk<NQ>(As, lda, W + (long)(nv ? n : 0) * D, nv, wid * (D / 4), acc);
   splitk_reduce(acc, red);
-  if (wid == 0 && nv) {
-    const float bias = j.bias[n];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (row < j.M) j.out[(long)row * j.V + n] = acc[r] + bias;
-    }
-  }
-}
-
-template <int NP, int FMT = 0>
-void launch_joiner_split(const JoinerArgs& j, hipStream_t st);
-
-void launch_joiner(const JoinerArgs& j, hipStream_t st) {
-  if (j.M <= 0) return;
-  if (j.Wx != nullptr) {  // split-bf16 modes (defined below)
-    ZASR_REQUIRE(j.pieces == 2 || j.pieces == 3 || j.pieces == kPiecesF16,
-                 "joiner: pieces must be 2, 3 or kPiecesF16");
-    if (j.pieces == 2)
-      launch_joiner_split<2>(j, st);
-    else if (j.pieces == 3)
-      launch_joiner_split<3>(j, st);
-    else
-      launch_joiner_split<2, 1>(j, st);
-    return;
-  }
-  ZASR_REQUIRE(j.D % 32 == 0 && j.D <= 512, "joiner_dim must be a multiple of 32, <= 512");
-  dim3 grid(cdiv(j.V, 32), cdiv(j.M, 32));
-  size_t lds = (32 * (j.D + 4) + 3 * 16 * 64) * sizeof(float);
-  switch (j.D / 32) {
-    case 2: ZASR_LAUNCH(joiner_kernel<2>, grid, dim3(256), lds, st, j); break;
-    case 4: ZASR_LAUNCH(joiner_kernel<4>, grid, dim3(256), lds, st, j); break;
-    case 8: ZASR_LAUNCH(joiner_kernel<8>, grid, dim3(256), lds, st, j); break;
-    case 16: ZASR_LAUNCH(joiner_kernel<16>, grid, dim3(256), lds, st, j); break;
-    default: throw std::runtime_error("joiner dim must be 64, 128, 256 or 512");
-  }
+  if (wid == 0) store_tile32(acc, j.bias, j.out, j.V, m0, j.M, n, j.V, lane >> 5);
 }
 
 // --------------------------------------------------------------------------------------
@@ -436,7 +470,7 @@ void launch_joiner(const JoinerArgs& j, hipStream_t st) {
 // through LDS.  Grid = V/32 x M/32 blocks (>= 250 at greedy batch 120: the whole chip).
 // --------------------------------------------------------------------------------------
 template <int NK>  // NK = D / 64 k16-steps per wave
-__global__ __launch_bounds__(256) void joiner_bf16_kernel(JoinerBf16Args j) {
+__global__ __launch_bounds__(256) void joiner_bf16_kernel(JoinerArgs j) {
   __shared__ float red[3 * 16 * 64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int col = lane & 31, h = lane >> 5;
@@ -447,8 +481,8 @@ __global__ __launch_bounds__(256) void joiner_bf16_kernel(JoinerBf16Args j) {
   const int D = j.D;
   const int ar = m0 + col < j.M ? m0 + col : j.M - 1;
   const int kb = wid * (D / 4) + 8 * h;
-  const __bf16* arow = j.J + (long)ar * D + kb;
-  const __bf16* brow = j.W + (long)(nv ? n : 0) * D + kb;
+  const __bf16* arow = reinterpret_cast<const __bf16*>(j.J) + (long)ar * D + kb;
+  const __bf16* brow = reinterpret_cast<const __bf16*>(j.W) + (long)(nv ? n : 0) * D + kb;
   bf16x8 a[NK], b[NK];
 #pragma unroll
   for (int q = 0; q < NK; ++q) {
@@ -461,31 +495,13 @@ __global__ __launch_bounds__(256) void joiner_bf16_kernel(JoinerBf16Args j) {
 #pragma unroll
   for (int q = 0; q < NK; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[q], b[q], acc, 0, 0, 0);
   splitk_reduce(acc, red);
-  if (wid != 0 || !nv) return;
-  const float bias = j.bias[n];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (row < j.M) j.out[(long)row * j.V + n] = acc[r] + bias;
-  }
-}
-
-void launch_joiner_bf16(const JoinerBf16Args& j, hipStream_t st) {
-  if (j.M <= 0) return;
-  dim3 grid(cdiv(j.V, 32), cdiv(j.M, 32));
-  switch (j.D) {
-    case 64: ZASR_LAUNCH(joiner_bf16_kernel<1>, grid, dim3(256), 0, st, j); break;
-    case 128: ZASR_LAUNCH(joiner_bf16_kernel<2>, grid, dim3(256), 0, st, j); break;
-    case 256: ZASR_LAUNCH(joiner_bf16_kernel<4>, grid, dim3(256), 0, st, j); break;
-    case 512: ZASR_LAUNCH(joiner_bf16_kernel<8>, grid, dim3(256), 0, st, j); break;
-    default: throw std::runtime_error("joiner dim must be 64, 128, 256 or 512");
-  }
+  if (wid == 0) store_tile32(acc, j.bias, j.out, j.V, m0, j.M, n, j.V, h);
 }
 
 // --------------------------------------------------------------------------------------
 // split-bf16 joiner (the bf16x3 / bf16x6 modes): J f32 split into NP bf16 pieces as it is
-// loaded, W_out pre-split (piece t at Wx + t V D); the products of the pieces (3 / 6 MFMAs per
-// k16 step) accumulate in f32 -- near-f32 / f32-quality logits at bf16 MFMA rates.  Same
+// loaded, W_out pre-split (piece t at W + t w_plane); the products of the pieces (3 / 6 MFMAs
+// per k16 step) accumulate in f32 -- near-f32 / f32-quality logits at bf16 MFMA rates.  Same
 // block / wave / split-K structure as joiner_bf16_kernel.
 // --------------------------------------------------------------------------------------
 template <int NK, int NP, int FMT = 0>
@@ -498,11 +514,11 @@ __global__ __launch_bounds__(256) void joiner_split_kernel(JoinerArgs j) {
   const int n = blockIdx.x * 32 + col;
   const bool nv = n < j.V;
   const int D = j.D;
-  const long blo = (long)j.V * D;
+  const long blo = j.w_plane;
   const int ar = m0 + col < j.M ? m0 + col : j.M - 1;
   const int kb = wid * (D / 4) + 8 * h;
-  const float* arow = j.J + (long)ar * D + kb;
-  const __bf16* brow = j.Wx + (long)(nv ? n : 0) * D + kb;
+  const float* arow = reinterpret_cast<const float*>(j.J) + (long)ar * D + kb;
+  const __bf16* brow = reinterpret_cast<const __bf16*>(j.W) + (long)(nv ? n : 0) * D + kb;
   float4 x0[NK], x1[NK];
   bf16x8 b[NP][NK];
 #pragma unroll
@@ -533,18 +549,51 @@ __global__ __launch_bounds__(256) void joiner_split_kernel(JoinerArgs j) {
     for (int r = 0; r < 16; ++r) acc[r] += accl[r] * kF16LoInv;
   }
   splitk_reduce(acc, red);
-  if (wid != 0 || !nv) return;
-  const float bias = j.bias[n];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (row < j.M) j.out[(long)row * j.V + n] = acc[r] + bias;
-  }
+  if (wid == 0) store_tile32(acc, j.bias, j.out, j.V, m0, j.M, n, j.V, h);
 }
 
-template <int NP, int FMT>
-void launch_joiner_split(const JoinerArgs& j, hipStream_t st) {
-  dim3 grid(cdiv(j.V, 32), cdiv(j.M, 32));
+// --------------------------------------------------------------------------------------
+// speculative-greedy / beam joiner on fragment-packed J / W (kernels.h JoinerArgs,
+// JOINER_PACKED).  Register-staged: no LDS.  Block = 64 x 64 outputs, wave = (row tile, column
+// group): each wave streams its own J row tile and W column group (1 KB coalesced fragment
+// loads, packed_tile_mma) -- twice the L2 reads of an LDS-shared tile, but a block needs no LDS
+// and few VGPRs, so under the batch pipeline it co-resides with the next batch's encoder GEMM
+// blocks instead of waiting for whole CUs to drain.
+template <int QK, int NP, int CH, int FMT>
+__device__ __forceinline__ void joiner_packed_block(const JoinerArgs& j) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int m0 = blockIdx.y * 64;
+  if (tile_done(j.live_t, j.live_len, j.live_f, m0, j.M) &&
+      (m0 + 32 >= j.M || tile_done(j.live_t, j.live_len, j.live_f, m0 + 32, j.M)))
+    return;  // block-uniform: every stream of these 64 rows has finished
+  const int rt = wid >> 1, gc = wid & 1;
+  const int row0 = m0 + 32 * rt;
+  const int g = blockIdx.x * 2 + gc;
+  if (row0 >= j.M || g * 32 >= j.V) return;
+  const bf16x8* srcJ = reinterpret_cast<const bf16x8*>(j.J) + (long)(row0 >> 5) * QK * 64 + lane;
+  const bf16x8* srcW = reinterpret_cast<const bf16x8*>(j.W) + (long)g * QK * 64 + lane;
+  f32x16 acc;
+  packed_tile_mma<QK, NP, CH, FMT>(srcJ, srcW, j.j_plane / 8, j.w_plane / 8, acc);
+  store_tile32(acc, j.bias, j.out, j.V, row0, j.M, g * 32 + (lane & 31), j.V, lane >> 5);
+}
+
+// bf16: 8 fragments of each operand in flight ahead of the MFMAs
+template <int QK>
+__global__ __launch_bounds__(256) void joiner_reg_kernel(JoinerArgs j) {
+  joiner_packed_block<QK, 1, 8, 0>(j);
+}
+
+// split-bf16 modes on packed pieces (written / packed once: store_j4, Engine load): CH k16
+// steps of the NP pieces of both fragments in flight per register set
+template <int QK, int NP, int CH, int FMT = 0>
+__global__ __launch_bounds__(256) void joiner_split_packed_kernel(JoinerArgs j) {
+  joiner_packed_block<QK, NP, CH, FMT>(j);
+}
+
+namespace {
+// the row-major split kernel by joiner dim
+template <int NP, int FMT = 0>
+void launch_joiner_split(const JoinerArgs& j, dim3 grid, hipStream_t st) {
   switch (j.D) {
     case 64: ZASR_LAUNCH((joiner_split_kernel<1, NP, FMT>), grid, dim3(256), 0, st, j); break;
     case 128: ZASR_LAUNCH((joiner_split_kernel<2, NP, FMT>), grid, dim3(256), 0, st, j); break;
@@ -554,137 +603,7 @@ void launch_joiner_split(const JoinerArgs& j, hipStream_t st) {
   }
 }
 
-// --------------------------------------------------------------------------------------
-// speculative-greedy / beam joiner on fragment-packed J / W (kernels.h JoinerPackedArgs).
-// Register-staged: no LDS.  Each wave streams its own J row tile and W column group (1 KB
-// coalesced fragment loads, 8 fragments of each in flight ahead of the MFMAs) -- twice the L2
-// reads of an LDS-shared tile, but a block needs no LDS and few VGPRs, so under the batch
-// pipeline it co-resides with the next batch's encoder GEMM blocks instead of waiting for whole
-// CUs to drain.
-template <int QK>
-__global__ __launch_bounds__(256) void joiner_reg_kernel(JoinerPackedArgs j) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int m0 = blockIdx.y * 64;
-  if (tile_done(j.live_t, j.live_len, j.live_f, m0, j.M) &&
-      (m0 + 32 >= j.M || tile_done(j.live_t, j.live_len, j.live_f, m0 + 32, j.M)))
-    return;  // block-uniform: every stream of these 64 rows has finished
-  const int rt = wid >> 1, gc = wid & 1;
-  const int row0 = m0 + 32 * rt;
-  const int g = blockIdx.x * 2 + gc;
-  if (row0 >= j.M || g * 32 >= j.V) return;
-  const bf16x8* srcJ = reinterpret_cast<const bf16x8*>(j.Jp) + (long)(row0 >> 5) * QK * 64 + lane;
-  const bf16x8* srcW = reinterpret_cast<const bf16x8*>(j.Wp) + (long)g * QK * 64 + lane;
-  constexpr int CH = 8;
-  constexpr int NCH = QK / CH;
-  bf16x8 a[2][CH], b[2][CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    a[0][c] = srcJ[c * 64];
-    b[0][c] = srcW[c * 64];
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-  for (int h = 0; h < NCH; ++h) {
-    const int cur = h & 1;
-    if (h + 1 < NCH) {
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        a[cur ^ 1][c] = srcJ[((h + 1) * CH + c) * 64];
-        b[cur ^ 1][c] = srcW[((h + 1) * CH + c) * 64];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][c], b[cur][c], acc, 0, 0, 0);
-  }
-  const int col = g * 32 + (lane & 31);
-  if (col >= j.V) return;
-  const float bb = j.bias[col];
-  const int hh = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-    if (row < j.M) j.out[(long)row * j.V + col] = acc[r] + bb;
-  }
-}
-
-// Split-bf16 modes on packed pieces: the joiner_reg_kernel structure (no LDS: co-resides with
-// the encoder blocks of the next batch), each k16 step loading the NP pieces of its J and W
-// fragments (written / packed once: store_j4, Engine load) and issuing the NP (NP + 1) / 2
-// piece products smallest first (mfma_split, the order of gemm_x3 / joiner_split_kernel).
-// CH k16 steps of fragments in flight per register set.
-template <int QK, int NP, int CH, int FMT = 0>
-__global__ __launch_bounds__(256) void joiner_split_packed_kernel(JoinerPackedArgs j) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int m0 = blockIdx.y * 64;
-  if (tile_done(j.live_t, j.live_len, j.live_f, m0, j.M) &&
-      (m0 + 32 >= j.M || tile_done(j.live_t, j.live_len, j.live_f, m0 + 32, j.M)))
-    return;  // block-uniform: every stream of these 64 rows has finished
-  const int rt = wid >> 1, gc = wid & 1;
-  const int row0 = m0 + 32 * rt;
-  const int g = blockIdx.x * 2 + gc;
-  if (row0 >= j.M || g * 32 >= j.V) return;
-  const bf16x8* srcJ = reinterpret_cast<const bf16x8*>(j.Jp) + (long)(row0 >> 5) * QK * 64 + lane;
-  const bf16x8* srcW = reinterpret_cast<const bf16x8*>(j.Wp) + (long)g * QK * 64 + lane;
-  const long jp = j.j_plane / 8, wp = j.w_plane / 8;  // planes in bf16x8 units
-  constexpr int NCH = QK / CH;
-  bf16x8 a[2][CH][NP], b[2][CH][NP];
-#pragma unroll
-  for (int c = 0; c < CH; ++c)
-#pragma unroll
-    for (int t = 0; t < NP; ++t) {
-      a[0][c][t] = srcJ[t * jp + c * 64];
-      b[0][c][t] = srcW[t * wp + c * 64];
-    }
-  f32x16 acc, accl;  // accl: the lo products (FMT 1, the f16x3 format)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = accl[r] = 0.f;
-  // the next set's loads go out as one group before this set's MFMAs (scheduling barriers:
-  // left alone, the compiler streams one load per MFMA with ~4 in flight, latency-bound)
-#pragma unroll
-  for (int h = 0; h < NCH; ++h) {
-    const int cur = h & 1;
-    if (h + 1 < NCH) {
-#pragma unroll
-      for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int t = 0; t < NP; ++t) {
-          a[cur ^ 1][c][t] = srcJ[t * jp + ((h + 1) * CH + c) * 64];
-          b[cur ^ 1][c][t] = srcW[t * wp + ((h + 1) * CH + c) * 64];
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      if constexpr (FMT == 1) {
-        const bf16x8 x[2] = {a[cur][c][0], a[cur][c][1]};
-        const bf16x8 y[2] = {b[cur][c][0], b[cur][c][1]};
-        mfma_h3(x, y, acc, accl);
-      } else {
-        acc = mfma_split<NP>(a[cur][c], b[cur][c], acc);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if constexpr (FMT == 1) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] += accl[r] * kF16LoInv;
-  }
-  const int col = g * 32 + (lane & 31);
-  if (col >= j.V) return;
-  const float bb = j.bias[col];
-  const int hh = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-    if (row < j.M) j.out[(long)row * j.V + col] = acc[r] + bb;
-  }
-}
-
-void launch_joiner_packed(const JoinerPackedArgs& j, hipStream_t st) {
-  if (j.M <= 0) return;
+void launch_joiner_packed(const JoinerArgs& j, hipStream_t st) {
   dim3 grid(cdiv(j.V, 64), cdiv(j.M, 64));
   if (j.pieces > 0) {
     ZASR_REQUIRE(j.pieces == 2 || j.pieces == 3 || j.pieces == kPiecesF16,
@@ -711,8 +630,47 @@ void launch_joiner_packed(const JoinerPackedArgs& j, hipStream_t st) {
     default: throw std::runtime_error("packed joiner: joiner dim must be 256 or 512");
   }
 }
+}  // namespace
 
-// element offset of J[row][k] in the fragment-packed image (kernels.h JoinerPackedArgs)
+// the kernel by J's layout, the operand format and the joiner dim (kernels.h JoinerArgs)
+void launch_joiner(const JoinerArgs& j, hipStream_t st) {
+  if (j.M <= 0) return;
+  if (j.layout == JOINER_PACKED) return launch_joiner_packed(j, st);
+  dim3 grid(cdiv(j.V, 32), cdiv(j.M, 32));
+  if (j.layout == JOINER_BF16) {
+    switch (j.D) {
+      case 64: ZASR_LAUNCH(joiner_bf16_kernel<1>, grid, dim3(256), 0, st, j); break;
+      case 128: ZASR_LAUNCH(joiner_bf16_kernel<2>, grid, dim3(256), 0, st, j); break;
+      case 256: ZASR_LAUNCH(joiner_bf16_kernel<4>, grid, dim3(256), 0, st, j); break;
+      case 512: ZASR_LAUNCH(joiner_bf16_kernel<8>, grid, dim3(256), 0, st, j); break;
+      default: throw std::runtime_error("joiner dim must be 64, 128, 256 or 512");
+    }
+    return;
+  }
+  ZASR_REQUIRE(j.layout == JOINER_F32, "joiner: unknown J layout");
+  if (j.pieces != 0) {  // split-bf16 modes
+    ZASR_REQUIRE(j.pieces == 2 || j.pieces == 3 || j.pieces == kPiecesF16,
+                 "joiner: pieces must be 2, 3 or kPiecesF16");
+    if (j.pieces == 2)
+      launch_joiner_split<2>(j, grid, st);
+    else if (j.pieces == 3)
+      launch_joiner_split<3>(j, grid, st);
+    else
+      launch_joiner_split<2, 1>(j, grid, st);
+    return;
+  }
+  ZASR_REQUIRE(j.D % 32 == 0 && j.D <= 512, "joiner_dim must be a multiple of 32, <= 512");
+  size_t lds = (32 * (j.D + 4) + 3 * 16 * 64) * sizeof(float);
+  switch (j.D / 32) {
+    case 2: ZASR_LAUNCH(joiner_kernel<2>, grid, dim3(256), lds, st, j); break;
+    case 4: ZASR_LAUNCH(joiner_kernel<4>, grid, dim3(256), lds, st, j); break;
+    case 8: ZASR_LAUNCH(joiner_kernel<8>, grid, dim3(256), lds, st, j); break;
+    case 16: ZASR_LAUNCH(joiner_kernel<16>, grid, dim3(256), lds, st, j); break;
+    default: throw std::runtime_error("joiner dim must be 64, 128, 256 or 512");
+  }
+}
+
+// element offset of J[row][k] in the fragment-packed image (kernels.h JoinerArgs)
 __device__ __forceinline__ long packed_j_off(long row, int k, int D) {
   const long rt = row >> 5;
   const int r = (int)(row & 31), q = k >> 4, hh = (k >> 3) & 1, j = k & 7;
@@ -1638,9 +1596,9 @@ void launch_greedy_spec(const SearchState& s, const float* logits, int V, int S,
 //
 // Block (x, rt) = 8 waves over the joiner rows of row tile rt (32 rows = streams 8 rt ..
 // 8 rt + 7, frames t_cur .. t_cur + 3) and the 256 vocabulary columns 256 x .. : wave w
-// computes the 32 x 32 tile of column group 8 x + w over all of D with exactly the MFMA
-// sequence of joiner_reg_kernel (bf16) / joiner_split_packed_kernel (f16x3), so the logits are
-// those of the two-launch path bit for bit.  The logits leave by write-through (sc1) stores;
+// computes the 32 x 32 tile of column group 8 x + w over all of D with packed_tile_mma, the
+// instance joiner_reg_kernel (bf16) / joiner_split_packed_kernel (f16x3) runs, so the logits
+// are those of the two-launch path bit for bit.  The logits leave by write-through (sc1) stores;
 // after every wave's stores have completed, lane 0 adds one to the tile's arrival counter
 // (agent scope) and the block that draws the last ticket runs the tile's greedy step, the
 // logits read back by sc1 loads (MI355X_MICROARCH.md, inter-workgroup hand-off: sc1 stores +
@@ -1667,7 +1625,7 @@ __global__ __launch_bounds__(512) void joiner_greedy_kernel(GreedyFusedArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rt = blockIdx.y, nct = gridDim.x;
-  const JoinerPackedArgs& j = a.j;
+  const JoinerArgs& j = a.j;
   if (blockIdx.x == 0 && rt == 0 && tid == 0) a.active[a.parity ^ 1] = 0;  // the next step's count
   const int m0 = rt * 32;
   if (tile_done(a.t_cur, a.enc_len, F, m0, j.M)) return;  // block-uniform: all 8 streams done
@@ -1676,71 +1634,10 @@ __global__ __launch_bounds__(512) void joiner_greedy_kernel(GreedyFusedArgs a) {
   // ---- joiner: wave w, column group g (32 columns), all 32 rows ----
   const int g = blockIdx.x * 8 + wid;
   if (g * 32 < j.V) {
-    const bf16x8* srcJ = reinterpret_cast<const bf16x8*>(j.Jp) + (long)rt * QK * 64 + lane;
-    const bf16x8* srcW = reinterpret_cast<const bf16x8*>(j.Wp) + (long)g * QK * 64 + lane;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if constexpr (FMT == 0) {  // bf16: joiner_reg_kernel's loop
-      constexpr int CH = 8, NCH = QK / CH;
-      bf16x8 aa[2][CH], bb[2][CH];
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        aa[0][c] = srcJ[c * 64];
-        bb[0][c] = srcW[c * 64];
-      }
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) {
-        const int cur = h & 1;
-        if (h + 1 < NCH) {
-#pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            aa[cur ^ 1][c] = srcJ[((h + 1) * CH + c) * 64];
-            bb[cur ^ 1][c] = srcW[((h + 1) * CH + c) * 64];
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aa[cur][c], bb[cur][c], acc, 0, 0, 0);
-      }
-    } else {  // f16x3: joiner_split_packed_kernel<QK, 2, 4, 1>'s loop
-      constexpr int CH = 4, NCH = QK / CH;
-      const long jp = j.j_plane / 8, wp = j.w_plane / 8;
-      bf16x8 aa[2][CH][2], bb[2][CH][2];
-#pragma unroll
-      for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          aa[0][c][t] = srcJ[t * jp + c * 64];
-          bb[0][c][t] = srcW[t * wp + c * 64];
-        }
-      f32x16 accl;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accl[r] = 0.f;
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) {
-        const int cur = h & 1;
-        if (h + 1 < NCH) {
-#pragma unroll
-          for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              aa[cur ^ 1][c][t] = srcJ[t * jp + ((h + 1) * CH + c) * 64];
-              bb[cur ^ 1][c][t] = srcW[t * wp + ((h + 1) * CH + c) * 64];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          const bf16x8 x[2] = {aa[cur][c][0], aa[cur][c][1]};
-          const bf16x8 y[2] = {bb[cur][c][0], bb[cur][c][1]};
-          mfma_h3(x, y, acc, accl);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] += accl[r] * kF16LoInv;
-    }
+    const bf16x8* srcJ = reinterpret_cast<const bf16x8*>(j.J) + (long)rt * QK * 64 + lane;
+    const bf16x8* srcW = reinterpret_cast<const bf16x8*>(j.W) + (long)g * QK * 64 + lane;
+    f32x16 acc;  // bf16: joiner_reg_kernel's instance; f16x3: joiner_split_packed_kernel<QK, 2, 4, 1>'s
+    packed_tile_mma<QK, FMT ? 2 : 1, FMT ? 4 : 8, FMT>(srcJ, srcW, j.j_plane / 8, j.w_plane / 8, acc);
     // + bias, then a 4 x 4 transpose inside each lane quad (two DPP butterfly steps) so that
     // every lane holds 4 consecutive columns of one row: 16-byte write-through stores (a 4-byte
     // sc1 store is one fabric write each, ~6x the 16-byte store's time per byte)
@@ -1966,12 +1863,13 @@ __global__ __launch_bounds__(512) void joiner_greedy_kernel(GreedyFusedArgs a) {
 
 void launch_joiner_greedy(const GreedyFusedArgs& a, hipStream_t st) {
   if (a.S <= 0) return;
-  const JoinerPackedArgs& j = a.j;
+  const JoinerArgs& j = a.j;
   ZASR_REQUIRE(j.M == a.S * 4, "joiner_greedy: 4 window rows per stream");
   ZASR_REQUIRE(j.V % 4 == 0 && j.V <= 2048, "joiner_greedy: vocabulary a multiple of 4, <= 2048");
   ZASR_REQUIRE(a.ldo >= j.V && a.ldo % 32 == 0, "joiner_greedy: logits row stride");
   ZASR_REQUIRE(j.D == 256 || j.D == 512, "joiner_greedy: joiner dim must be 256 or 512");
-  ZASR_REQUIRE(a.dt.D == j.D && a.dt.j_packed, "joiner_greedy: packed J of the joiner's dim");
+  ZASR_REQUIRE(a.dt.D == j.D && a.dt.j_packed && j.layout == JOINER_PACKED,
+               "joiner_greedy: packed J of the joiner's dim");
   ZASR_REQUIRE(j.pieces == 0 || j.pieces == kPiecesF16, "joiner_greedy: bf16 or f16x3 operands");
   ZASR_REQUIRE((long)j.M * a.ldo * 4 < 0x7fffffffL, "joiner_greedy: logits beyond 2 GB");
   const dim3 grid(cdiv(j.V, 256), cdiv(a.S, 8));

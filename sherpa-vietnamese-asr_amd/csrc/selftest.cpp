@@ -4,7 +4,8 @@
 // incidentally (tail tiles, M < 16, every K / D and epilogue) against a float64 product on the
 // host; the fused FFNs also out of place, the fused stack seam beside the kernels it
 // replaces, and the convolution path's hand-written kernels (ConvolutionModule depthwise conv,
-// conv.0, the ConvNeXt block) and BiasNorm on ragged batches given as per-sequence lengths.
+// conv.0, the ConvNeXt block) and BiasNorm on ragged batches given as per-sequence lengths, and
+// the joiner kernels on row-major and on host-packed J.
 // Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
 #include <cstring>
 #include <memory>
@@ -500,6 +501,92 @@ void selftest_bias_norm(int rows, int d, const float* bias, float log_scale, flo
   ox.down(x, "bias_norm");
   if (oo) oo->down(orig, "bias_norm");
   if (oc) oc->down(copy_out, "bias_norm");
+}
+
+// ---- the joiner kernels ----
+namespace {
+// J [M][D] as the search kernels leave it for the packed joiner (kernels.h JoinerArgs; written
+// here from that description, not with the device packer): element (row, k) of an image at
+// ((row / 32 * (D / 16) + k / 16) * 64 + row % 32 + 32 * (k / 8 % 2)) * 8 + k % 8, `rows` rows a
+// multiple of 64, one image per stored piece.  Pieces as store_j4 writes them: bf16 (pieces 0),
+// successive bf16 residuals, or the fp16 hi piece and (x - hi) * 2^11.  Rows past M hold `pad`.
+std::vector<__bf16> pack_j_host(const float* J, int M, int D, long rows, int pieces, float pad) {
+  const int np = pieces ? stored_pieces(pieces) : 1;
+  const size_t plane = (size_t)rows * D;
+  std::vector<__bf16> img(plane * np);
+  for (long row = 0; row < rows; ++row)
+    for (int k = 0; k < D; ++k) {
+      const size_t at = ((size_t)((row / 32) * (D / 16) + k / 16) * 64 + row % 32 + 32 * (k / 8 % 2)) * 8 + k % 8;
+      float x = row < M ? J[(size_t)row * D + k] : pad;
+      if (pieces == kPiecesF16) {
+        const _Float16 hi = (_Float16)x, lo = (_Float16)((x - (float)hi) * 2048.f);
+        std::memcpy(&img[at], &hi, 2);
+        std::memcpy(&img[plane + at], &lo, 2);
+        continue;
+      }
+      for (int t = 0; t < np; ++t) {
+        const __bf16 v = (__bf16)x;
+        img[t * plane + at] = v;
+        x -= (float)v;
+      }
+    }
+  return img;
+}
+}  // namespace
+
+void selftest_joiner(int mode, int layout, int M, int V, int D, const float* J, const float* W,
+                     const float* bias, const int* live_t, const int* live_len, int live_f,
+                     float* out) {
+  const bool f32 = mode == ZASR_PRECISION_FP32, h16 = mode == ZASR_PRECISION_BF16;
+  const int pieces = mode == ZASR_PRECISION_BF16X3   ? 2
+                     : mode == ZASR_PRECISION_BF16X6 ? 3
+                     : mode == ZASR_PRECISION_F16X3  ? kPiecesF16
+                                                     : 0;
+  ZASR_REQUIRE(f32 || h16 || pieces != 0,
+               "selftest joiner: mode must be ZASR_PRECISION_FP32, _BF16, _BF16X3, _BF16X6 or _F16X3");
+  ZASR_REQUIRE(layout == 0 || (layout == 1 && !f32), "selftest joiner: layout 0, or 1 outside fp32");
+  ZASR_REQUIRE(M >= 1 && V >= 1 && D >= 16 && D % 16 == 0, "selftest joiner: M, V >= 1, D % 16 == 0");
+  const int np = pieces ? stored_pieces(pieces) : 1;
+  const size_t nj = (size_t)M * D, nw = (size_t)V * D;
+  // W as the loader prepares it (engine_load.cpp): bf16, or the split pieces; layout 1: every
+  // piece in fragment order
+  const size_t pe = layout == 1 ? (size_t)gemm_rp_packed_elems(V, D) : 0;
+  DevBuf dW(nw * 4), dWx(nw * 2 * np), dWp(pe * 2 * np), dB((size_t)V * 4);
+  up(dW, W, nw * 4);
+  up(dB, bias, (size_t)V * 4);
+  if (h16) convert_to_bf16(dW.as<float>(), dWx.p, (long)nw, nullptr);
+  if (pieces) split_to_bf16(dW.as<float>(), dWx.p, (long)nw, pieces, nullptr);
+  for (int t = 0; layout == 1 && t < np; ++t)
+    gemm_rp_pack_weights(dWx.as<__bf16>() + t * nw, V, D, dWp.as<__bf16>() + t * pe, nullptr);
+  // J as its producers leave it (decjoin_kernel row-major, store_j4 packed)
+  const long jrows = joiner_packed_rows(M);
+  DevBuf dJ(layout == 1 ? (size_t)jrows * D * 2 * np : nj * 4);
+  if (layout == 1) {
+    const std::vector<__bf16> img = pack_j_host(J, M, D, jrows, pieces, 0.75f);
+    up(dJ, img.data(), img.size() * 2);
+  } else if (h16) {
+    up(dJ, round16(J, nj).data(), nj * 2);
+  } else {
+    up(dJ, J, nj * 4);
+  }
+  const int ns = live_t ? (M + live_f - 1) / live_f : 0;
+  DevBuf dT((size_t)ns * 4), dL((size_t)ns * 4);
+  if (live_t) {
+    up(dT, live_t, (size_t)ns * 4);
+    up(dL, live_len, (size_t)ns * 4);
+  }
+  OutBuf o(out, (size_t)M * V, V, false);  // a skipped tile keeps the caller's values
+  JoinerArgs ja{dJ.p, layout == 1 ? dWp.p : f32 ? dW.p : dWx.p, dB.as<float>(), o.as<float>(), M, V, D};
+  ja.layout = layout == 1 ? JOINER_PACKED : h16 ? JOINER_BF16 : JOINER_F32;
+  ja.pieces = pieces;
+  ja.j_plane = jrows * D;
+  ja.w_plane = layout == 1 ? (long)pe : (long)nw;
+  ja.live_t = live_t ? dT.as<int>() : nullptr;
+  ja.live_len = live_t ? dL.as<int>() : nullptr;
+  ja.live_f = live_t ? live_f : 0;
+  launch_joiner(ja, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(out, "joiner");
 }
 
 }  // namespace zasr

@@ -696,6 +696,26 @@ int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t ep
   });
 }
 
+int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int32_t D,
+                         const float* J, const float* W, const float* bias,
+                         const int32_t* live_t, const int32_t* live_len, int32_t live_f,
+                         float* out) {
+  if (!J || !W || !bias || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (M < 1 || V < 1) return fail(ZASR_ERR_INVALID, "M and V must be positive");
+  if ((live_t == nullptr) != (live_len == nullptr) || (live_t != nullptr && live_f < 1))
+    return fail(ZASR_ERR_INVALID, "the live filter takes live_t, live_len and live_f >= 1");
+  const bool split = mode == ZASR_PRECISION_BF16X3 || mode == ZASR_PRECISION_BF16X6 ||
+                     mode == ZASR_PRECISION_F16X3;
+  const bool ok0 = layout == 0 && (mode == ZASR_PRECISION_FP32 || mode == ZASR_PRECISION_BF16 || split) &&
+                   (D == 64 || D == 128 || D == 256 || D == 512);
+  const bool ok1 = layout == 1 && (mode == ZASR_PRECISION_BF16 || split) && (D == 256 || D == 512);
+  if (!ok0 && !ok1) return fail(ZASR_ERR_INVALID, "unsupported joiner mode / layout / dim");
+  return guarded([&]() {
+    zasr::selftest_joiner(mode, layout, M, V, D, J, W, bias, live_t, live_len, live_f, out);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const float* W1,
                          const float* b1, const float* W2, const float* b2,
                          const float* byp_orig, const float* byp_scale, float* X) {

@@ -37,7 +37,7 @@ EXPORTS = (
     "zasr_fbank_set_mel_banks", "zasr_selftest_launch", "zasr_decode_host_batches",
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
-    "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm",
+    "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm", "zasr_selftest_joiner",
     "zasr_selftest_dwconv1d", "zasr_selftest_conv1", "zasr_selftest_convnext",
     "zasr_selftest_bias_norm",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
@@ -226,6 +226,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_gemm_h3r.restype = C.c_int
     lib.zasr_selftest_gemm.argtypes = [I32] * 7 + [fp] * 7
     lib.zasr_selftest_gemm.restype = C.c_int
+    lib.zasr_selftest_joiner.argtypes = [I32] * 5 + [fp] * 3 + [C.POINTER(I32)] * 2 + [I32, fp]
+    lib.zasr_selftest_joiner.restype = C.c_int
     lib.zasr_selftest_ffn_h3.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, fp]
     lib.zasr_selftest_ffn_h3.restype = C.c_int
     lib.zasr_selftest_ffn_bf16.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, I32]
@@ -352,6 +354,23 @@ def selftest_gemm(mode: str, A, W, bias, C, epi: int = 0, a_bf16: bool = False,
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return C
+
+
+def selftest_joiner(mode: str, J, W, bias, out, layout: int = 0, live_t=None, live_len=None,
+                    live_f: int = 0, lib_path: Optional[str] = None) -> np.ndarray:
+    """The joiner kernels alone on one host problem (zasr_selftest_joiner; mode: a PRECISIONS
+    name; layout 0: row-major J, 1: fragment-packed J and W): returns out [M][V] after
+    out = J W^T + bias; rows of tiles the finished-stream filter skips keep out's values."""
+    lib = load_library(lib_path)
+    J, W, bias, out = _f32(J), _f32(W), _f32(bias), _f32(out).copy()
+    live = [None if x is None else np.ascontiguousarray(x, np.int32) for x in (live_t, live_len)]
+    p = lambda x: x.ctypes.data_as(C_FP)
+    ip = lambda x: None if x is None else x.ctypes.data_as(C.POINTER(C.c_int32))
+    rc = lib.zasr_selftest_joiner(PRECISIONS[mode], int(layout), J.shape[0], W.shape[0], J.shape[1],
+                                  p(J), p(W), p(bias), ip(live[0]), ip(live[1]), int(live_f), p(out))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out
 
 
 def selftest_ffn_h3(Y, W1, b1, W2, b2, X, byp_orig=None, byp_scale=None,
