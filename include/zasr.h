@@ -318,6 +318,50 @@ int32_t zasr_vad_last_passes(const zasr_vad* h);
 int zasr_vad_window(zasr_vad* h, const float* input, const float* state, int32_t n, float* prob,
                     float* state_out);
 
+/* ---- PyanNet segmentation ----
+   Replaces the reference diarizer's pyannote segmentation session
+   (core/speaker_diarization_senko_campp_optimized.py:383-396, pinned there to the CPU
+   provider) and the chunk batching around it (:413-437).  model_dir holds config.json +
+   model.safetensors (pyannote PyanNet state-dict names, the sinc filter bank as the plain
+   tensor sincnet.conv1d.0.weight [80][1][251]); reading the reference's
+   segmentation-community-1.onnx is not supported.  Bad arguments (null pointers, n <= 0,
+   fewer than 1261 samples per chunk) return ZASR_ERR_INVALID, missing model files
+   ZASR_ERR_NOT_FOUND. */
+typedef struct zasr_seg zasr_seg;
+int zasr_seg_create(const char* model_dir, int32_t device_id, zasr_seg** out);
+void zasr_seg_destroy(zasr_seg* h);
+/* Host-only.  Output frames per chunk of chunk_samples samples (589 at 160000; the reference's
+   NUM_SEG_FRAMES, core/speaker_diarization_pure_ort.py:114); 0 when chunk_samples is too short
+   for a frame, and chunks need at least 2 (1261 samples). */
+int32_t zasr_seg_num_frames(const zasr_seg* h, int64_t chunk_samples);
+/* seg_sess.run(None, {"input_values": batch})[0] (:435): batch [n][T] -> log-probabilities
+   [n][F][7], host buffers.  A chunk's result does not depend on the batch it is in. */
+int zasr_seg_logits(zasr_seg* h, const float* batch, int32_t n, int32_t T, float* logits);
+/* A whole file from the 16 kHz HBM signal d_audio[0, total): chunks of chunk_samples every
+   step_samples, starts as in :418-424 (0, step, ... up to the first start with start + chunk >=
+   total), zeros past the end of the signal (:430-434).  classes (host) [n_chunks][F] = the
+   argmax over the 7 powerset classes, lowest index on ties (:443); d_logits (device,
+   [n_chunks][F][7]) may be null.  Ordered after `stream` (a hipStream_t, 0 = none);
+   synchronises before it returns.  Bit-identical to zasr_seg_logits on the same chunks. */
+int zasr_seg_classes_device(zasr_seg* h, const float* d_audio, int64_t total,
+                            int32_t chunk_samples, int32_t step_samples, uint8_t* classes,
+                            float* d_logits, void* stream);
+/* number of chunks zasr_seg_classes_device makes of `total` samples (host-only) */
+int64_t zasr_seg_num_chunks(int64_t total, int32_t chunk_samples, int32_t step_samples);
+/* diagnostics of the recurrence: sequences per workgroup of the last call, and a forced value
+   (1, 2, 4, 8, 16; 0 = automatic).  Results do not depend on it. */
+int32_t zasr_seg_last_group(const zasr_seg* h);
+int zasr_seg_set_group(zasr_seg* h, int32_t group);
+/* The handle keeps its activation workspace between calls, as large as the longest file it has
+   seen (8.6 MB per 10 s chunk, at most the 8 GiB launch-group bound: 6.2 GB after an hour).
+   zasr_seg_trim frees it; the next call allocates what it needs. */
+int zasr_seg_trim(zasr_seg* h);
+/* stage timing on HIP events (off by default): with it on, every call synchronises and leaves
+   the milliseconds of its front (gather + input norm + sinc conv + pool + norm), convs,
+   LSTM input projections, recurrence and head in ms5[0..4] (tools/seg_bench.py) */
+int zasr_seg_set_profile(zasr_seg* h, int32_t on);
+int zasr_seg_stage_ms(zasr_seg* h, float* ms5);
+
 /* ---- device audio front end --------------------------------------------------------------
    Raw PCM -> the 16 kHz mono float32 HBM signal that zasr_decode_device,
    zasr_vad_probs_device and zasr_campp_windows_device read, and the reference's level

@@ -72,6 +72,12 @@ class Workspace {
     }
     return reinterpret_cast<T*>(b.p);
   }
+  // free every buffer; the caller has synchronised the work that used them
+  void clear() {
+    for (auto& kv : bufs_)
+      if (kv.second.p) ZASR_HIP_CHECK(hipFree(kv.second.p));
+    bufs_.clear();
+  }
 
  private:
   struct Buf {

@@ -25,6 +25,7 @@ enum GemmEpi : int {
   EPI_GELU = 7,     // C = v * Phi(v) = 0.5 v (1 + erf(v / sqrt 2))  (gemm_f32 only: ViBERT FFN)
   EPI_GLU = 8,      // C[m, n / 2] = v[2c] * sigmoid(v[2c + 1]) (gemm_x3 only: the conv modules'
                     // in_proj with interleaved weight rows; N = 2 x the output width, ldc = N / 2)
+  EPI_LEAKY = 9,    // C = v > 0 ? v : 0.01 v  (gemm_f32 only: the segmentation head's linears)
 };
 
 enum GemmALoad : int {

@@ -205,6 +205,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_f32_kernel(GemmPar
         if constexpr (EPI == EPI_SWOOSHR) v = swooshr(v);
         if constexpr (EPI == EPI_RELU) v = fmaxf(v, 0.f);
         if constexpr (EPI == EPI_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+        if constexpr (EPI == EPI_LEAKY) v = v > 0.f ? v : 0.01f * v;
         if constexpr (EPI == EPI_MULAUX) v *= aux[(long)row * p.ldaux + col];
         if constexpr (EPI == EPI_RESADD) v += *dst;
         *dst = v;
@@ -927,6 +928,7 @@ void gemm_f32(const GemmParams& p, int epi, int aload, bool b_ncontig, hipStream
       case EPI_RESADD: return launch_tile<ALOAD_DENSE, false, EPI_RESADD>(p, st);
       case EPI_RELU: return launch_tile<ALOAD_DENSE, false, EPI_RELU>(p, st);
       case EPI_GELU: return launch_tile<ALOAD_DENSE, false, EPI_GELU>(p, st);
+      case EPI_LEAKY: return launch_tile<ALOAD_DENSE, false, EPI_LEAKY>(p, st);
       case EPI_MULAUX: return launch_tile<ALOAD_DENSE, false, EPI_MULAUX>(p, st);
       default: break;
     }
@@ -948,6 +950,7 @@ void gemm_f32(const GemmParams& p, int epi, int aload, bool b_ncontig, hipStream
     ZASR_REQUIRE(p.i2c.C > 0 && p.i2c.C % 4 == 0 && p.i2c.Tout > 0 && p.K % p.i2c.C == 0 &&
                      (long)p.M % p.i2c.Tout == 0,
                  "gemm_f32: bad ALOAD_IM2COL1D geometry");
+    if (epi == EPI_NONE) return launch_tile<ALOAD_IM2COL1D, false, EPI_NONE>(p, st);
     if (epi == EPI_RELU) return launch_tile<ALOAD_IM2COL1D, false, EPI_RELU>(p, st);
     if (epi == EPI_MULAUX) return launch_tile<ALOAD_IM2COL1D, false, EPI_MULAUX>(p, st);
   }

@@ -13,6 +13,7 @@
 #include "campp.h"
 #include "common.h"
 #include "diar.h"
+#include "seg.h"
 #include "vad.h"
 #include "vibert.h"
 #include "engine.h"
@@ -58,6 +59,10 @@ struct zasr_vibert {
 
 struct zasr_vad {
   std::unique_ptr<zasr::VadEngine> eng;
+};
+
+struct zasr_seg {
+  std::unique_ptr<zasr::SegEngine> eng;
 };
 
 struct zasr_audio {
@@ -322,6 +327,95 @@ int zasr_vad_window(zasr_vad* h, const float* input, const float* state, int32_t
   return guarded([&]() {
     std::lock_guard<std::mutex> lk(h->eng->mu);
     h->eng->window_host(input, state, n, prob, state_out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_seg_create(const char* model_dir, int32_t device_id, zasr_seg** out) {
+  if (!model_dir || !out) return fail(ZASR_ERR_INVALID, "null model_dir/out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_seg;
+    try {
+      h->eng.reset(new zasr::SegEngine(model_dir, device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_seg_destroy(zasr_seg* h) { delete h; }
+
+int32_t zasr_seg_num_frames(const zasr_seg*, int64_t chunk_samples) {
+  return zasr::SegEngine::num_frames((long)chunk_samples);
+}
+
+int64_t zasr_seg_num_chunks(int64_t total, int32_t chunk_samples, int32_t step_samples) {
+  if (total <= 0 || chunk_samples <= 0 || step_samples <= 0) return 0;
+  return (int64_t)zasr::SegEngine::chunk_starts((long)total, chunk_samples, step_samples).size();
+}
+
+int32_t zasr_seg_last_group(const zasr_seg* h) { return h ? h->eng->last_group() : 0; }
+
+int zasr_seg_set_group(zasr_seg* h, int32_t group) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  if (group != 0 && group != 1 && group != 2 && group != 4 && group != 8 && group != 16)
+    return fail(ZASR_ERR_INVALID, "segmentation: group must be 0 (automatic), 1, 2, 4, 8 or 16");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_group(group);
+  return ZASR_OK;
+}
+
+int zasr_seg_trim(zasr_seg* h) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->trim();
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_seg_set_profile(zasr_seg* h, int32_t on) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_profile(on != 0);
+  return ZASR_OK;
+}
+
+int zasr_seg_stage_ms(zasr_seg* h, float* ms5) {
+  if (!h || !ms5) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  std::memcpy(ms5, h->eng->stage_ms(), sizeof(float) * zasr::SegEngine::kStages);
+  return ZASR_OK;
+}
+
+int zasr_seg_logits(zasr_seg* h, const float* batch, int32_t n, int32_t T, float* logits) {
+  if (n <= 0) return fail(ZASR_ERR_INVALID, "segmentation: n must be positive");
+  if (T < zasr::SegEngine::kMinSamples)
+    return fail(ZASR_ERR_INVALID, "segmentation: a chunk needs at least 1261 samples (2 frames)");
+  if (!h || !batch || !logits) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->logits_host(batch, n, T, logits);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_seg_classes_device(zasr_seg* h, const float* d_audio, int64_t total,
+                            int32_t chunk_samples, int32_t step_samples, uint8_t* classes,
+                            float* d_logits, void* stream) {
+  if (chunk_samples < zasr::SegEngine::kMinSamples)
+    return fail(ZASR_ERR_INVALID, "segmentation: a chunk needs at least 1261 samples (2 frames)");
+  if (step_samples <= 0) return fail(ZASR_ERR_INVALID, "segmentation: step must be positive");
+  if (!h || total < 0 || (total > 0 && (!d_audio || !classes)))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->classes_device(d_audio, (long)total, chunk_samples, step_samples, classes, d_logits,
+                           reinterpret_cast<hipStream_t>(stream));
     return (int)ZASR_OK;
   });
 }

@@ -29,6 +29,9 @@ EXPORTS = (
     "zasr_vibert_num_detect", "zasr_vibert_run",
     "zasr_vad_create", "zasr_vad_destroy", "zasr_vad_probs", "zasr_vad_probs_device",
     "zasr_vad_window", "zasr_vad_last_passes", "zasr_silence_flags",
+    "zasr_seg_create", "zasr_seg_destroy", "zasr_seg_num_frames", "zasr_seg_logits",
+    "zasr_seg_classes_device", "zasr_seg_num_chunks", "zasr_seg_last_group", "zasr_seg_set_group",
+    "zasr_seg_set_profile", "zasr_seg_stage_ms", "zasr_seg_trim",
     "zasr_create_stream", "zasr_destroy_stream", "zasr_stream_accept_waveform",
     "zasr_decode_stream", "zasr_decode_streams", "zasr_stream_is_decoded",
     "zasr_stream_num_tokens", "zasr_stream_num_frames", "zasr_stream_tokens",
@@ -188,6 +191,28 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_vad_window.restype = C.c_int
     lib.zasr_vad_last_passes.argtypes = [P]
     lib.zasr_vad_last_passes.restype = I32
+    lib.zasr_seg_create.argtypes = [C.c_char_p, I32, C.POINTER(P)]
+    lib.zasr_seg_create.restype = C.c_int
+    lib.zasr_seg_destroy.argtypes = [P]
+    lib.zasr_seg_destroy.restype = None
+    lib.zasr_seg_num_frames.argtypes = [P, I64]
+    lib.zasr_seg_num_frames.restype = I32
+    lib.zasr_seg_logits.argtypes = [P, fp, I32, I32, fp]
+    lib.zasr_seg_logits.restype = C.c_int
+    lib.zasr_seg_classes_device.argtypes = [P, P, I64, I32, I32, C.POINTER(C.c_uint8), P, P]
+    lib.zasr_seg_classes_device.restype = C.c_int
+    lib.zasr_seg_num_chunks.argtypes = [I64, I32, I32]
+    lib.zasr_seg_num_chunks.restype = I64
+    lib.zasr_seg_last_group.argtypes = [P]
+    lib.zasr_seg_last_group.restype = I32
+    lib.zasr_seg_set_group.argtypes = [P, I32]
+    lib.zasr_seg_set_group.restype = C.c_int
+    lib.zasr_seg_trim.argtypes = [P]
+    lib.zasr_seg_trim.restype = C.c_int
+    lib.zasr_seg_set_profile.argtypes = [P, I32]
+    lib.zasr_seg_set_profile.restype = C.c_int
+    lib.zasr_seg_stage_ms.argtypes = [P, fp]
+    lib.zasr_seg_stage_ms.restype = C.c_int
     lib.zasr_silence_flags.argtypes = [P, I64, I32, C.c_float, P, P]
     lib.zasr_silence_flags.restype = C.c_int
     # offline streams (the sherpa-onnx OfflineStream surface, zasr/offline.py)
@@ -1060,6 +1085,109 @@ class VadSession:
                                              st.ctypes.data_as(fp), n, p.ctypes.data_as(fp),
                                              so.ctypes.data_as(fp)))
         return [p[:, None], so]
+
+
+class SegSession:
+    """PyanNet segmentation on the GPU.  run(None, {"input_values": batch
+    [n, 1, T]}) -> [log-probabilities [n, F, 7]] is the onnxruntime session surface, so
+    `diarizer.seg_sess = SegSession(model_dir)` serves the reference's own _pyannote_vad
+    (core/speaker_diarization_senko_campp_optimized.py:435); classes_device() runs every chunk
+    of a file from the 16 kHz signal already in HBM."""
+
+    CHUNK = 160000   # :413
+    STEP = 80000     # :415
+    MIN_SAMPLES = 1261
+
+    def __init__(self, model_dir: str, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        rc = self.lib.zasr_seg_create(model_dir.encode(), device_id, C.byref(h))
+        if rc != 0:
+            msg = self.lib.zasr_last_error().decode()
+            if rc == 2:
+                raise FileNotFoundError(msg)
+            raise ZasrError(msg)
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_seg_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def num_frames(self, chunk_samples: int) -> int:
+        return int(self.lib.zasr_seg_num_frames(self.handle, int(chunk_samples)))
+
+    def num_chunks(self, total: int, chunk_samples: int = CHUNK, step_samples: int = STEP) -> int:
+        return int(self.lib.zasr_seg_num_chunks(int(total), int(chunk_samples), int(step_samples)))
+
+    @property
+    def last_group(self) -> int:
+        """Sequences per recurrence workgroup of the last call (diagnostic)."""
+        return int(self.lib.zasr_seg_last_group(self.handle))
+
+    def set_group(self, group: int) -> None:
+        """Force the recurrence group (1, 2, 4, 8, 16; 0 = automatic).  Results do not change."""
+        self._check(self.lib.zasr_seg_set_group(self.handle, int(group)))
+
+    def trim(self) -> None:
+        """Free the activation workspace the handle keeps between calls (8.6 MB per 10 s chunk
+        of the longest file seen, at most 8 GiB)."""
+        self._check(self.lib.zasr_seg_trim(self.handle))
+
+    STAGES = ("front", "convs", "projections", "recurrence", "head")
+
+    def set_profile(self, on: bool) -> None:
+        self._check(self.lib.zasr_seg_set_profile(self.handle, int(bool(on))))
+
+    def stage_ms(self) -> dict:
+        """Milliseconds of the last call's stages (after set_profile(True))."""
+        ms = (C.c_float * 5)()
+        self._check(self.lib.zasr_seg_stage_ms(self.handle, ms))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    def logits(self, batch: np.ndarray) -> np.ndarray:
+        x = np.ascontiguousarray(batch, np.float32)
+        if x.ndim == 3 and x.shape[1] == 1:
+            x = x[:, 0, :]
+        if x.ndim != 2:
+            raise ZasrError("segmentation session: input_values [n, 1, T] or [n, T]")
+        n, T = x.shape
+        if n <= 0 or T < self.MIN_SAMPLES:
+            raise ZasrError(f"segmentation session: n >= 1 and T >= {self.MIN_SAMPLES} "
+                            f"(got n = {n}, T = {T})")
+        x = np.ascontiguousarray(x)
+        out = np.empty((n, self.num_frames(T), 7), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.zasr_seg_logits(self.handle, x.ctypes.data_as(fp), n, T,
+                                             out.ctypes.data_as(fp)))
+        return out
+
+    def run(self, output_names, feeds):
+        return [self.logits(feeds["input_values"])]
+
+    def classes_device(self, d_audio: int, total: int, chunk_samples: int = CHUNK,
+                       step_samples: int = STEP, d_logits: int = 0, stream: int = 0) -> np.ndarray:
+        """Class map [n_chunks, F] (uint8) of the signal d_audio[0, total) (a device pointer);
+        d_logits (device, [n_chunks, F, 7] float32) is filled when given."""
+        if chunk_samples < self.MIN_SAMPLES:
+            raise ZasrError(f"segmentation session: chunks need >= {self.MIN_SAMPLES} samples")
+        n = self.num_chunks(total, chunk_samples, step_samples)
+        out = np.empty((n, self.num_frames(chunk_samples)), np.uint8)
+        if n:
+            self._check(self.lib.zasr_seg_classes_device(
+                self.handle, C.c_void_p(d_audio), int(total), int(chunk_samples), int(step_samples),
+                out.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(d_logits), C.c_void_p(stream)))
+        return out
 
 
 AUDIO_FORMATS = {"float32": 0, "int16": 1}  # include/zasr.h ZASR_AUDIO_F32 / ZASR_AUDIO_I16

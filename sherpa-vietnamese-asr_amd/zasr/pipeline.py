@@ -121,15 +121,25 @@ class FullPipe:
     CamppEmbedder; vib: VibertSession (ONNX session surface); vib_vocab: ViBERT vocabulary
     size incl. START."""
 
+    seg = None              # the segmentation session (set by __init__; None: planner regions)
+    overlap_regions = None  # set by prepare() when a segmentation session is given
+
     def __init__(self, rec, recd, emb, vib, vib_vocab: int, beam: int = 1,
                  campp_batch: int = 4096, iterations: int = ITERATIONS, vib_batch: int = 0,
                  tokenizer=None, confidence: float = 0.3, case_confidence: float = 0.0,
-                 shard: bool = False, diarize: bool = False):
+                 shard: bool = False, diarize: bool = False, segmentation=None):
         """diarize: cluster each pass's window embeddings into speakers (zasr.diarize: the
         reference's process() from the clustering on, :726-830) and add "speaker_segments"
         (who spoke when: [{"start", "end", "speaker"}]) and "speaker_labels" (one per window)
         to the pass's dict.  The spectral embedding runs on the CAM++ stream straight from the
         device embeddings (with `shard`, from the gathered embeddings on every rank).
+
+        segmentation: a zasr.binding.SegSession, or None (the default: nothing changes).  With a
+        session the speech regions the CAM++ windows are cut from are the reference's first
+        diarization stage (zasr.segmentation.pyannote_vad on the signal already in HBM:
+        _pyannote_vad, core/speaker_diarization_senko_campp_optimized.py:411-517) instead of
+        the chunk planner's, region bounds int(seconds * 16000) as at :543-544, and every
+        pass's dict gains "overlap_regions" ([(start_s, end_s)], :403-409).
 
         shard: strong scaling over the ranks of an initialised torch.distributed group (one
         process per GPU, every rank given the same file): each rank decodes its
@@ -142,6 +152,8 @@ class FullPipe:
         self.rec, self.recd, self.emb, self.vib = rec, recd, emb, vib
         self.vib_vocab, self.beam, self.B, self.iterations = vib_vocab, beam, campp_batch, iterations
         self.shard = bool(shard)
+        self.seg = segmentation
+        self.overlap_regions = None
         self.diar = None
         if diarize:
             import torch
@@ -187,7 +199,16 @@ class FullPipe:
             a = np.ascontiguousarray(audio, np.float32)
         self.n = a.shape[0]
         plan = plan_chunks(a)                      # decode chunks, 3 s overlap
-        regions = plan_chunks(a, overlap_sec=0.0)  # diarization speech regions
+        d_early = None
+        self.overlap_regions = None
+        if self.seg is None:
+            regions = plan_chunks(a, overlap_sec=0.0)  # diarization speech regions
+        else:  # the segmentation reads the signal in HBM: upload it here, not below
+            from zasr.segmentation import pyannote_vad
+            d_early = d_front if front else torch.from_numpy(a).cuda()
+            speech = pyannote_vad(d_early, self.seg)
+            regions = [(int(s * 16000), min(int(e * 16000), self.n), 0) for s, e in speech]
+            self.overlap_regions = list(speech.overlap_regions)
         self.c_off_all = [s for s, _, _ in plan]
         self.c_len_all = [e - s for s, e, _ in plan]
         self.r_off_all = [s for s, _, _ in regions]
@@ -209,6 +230,8 @@ class FullPipe:
         # window count bound: (frames - 150) / 60 + 2 per region
         self.cap = max(1, sum(max(1, (n // 160) // 60 + 2) for n in self.r_len))
         self.d_audio = d_front if front else torch.from_numpy(a).cuda()
+        if d_early is not None:
+            self.d_audio = d_early
         self.d_feats = torch.empty((self.cap, 150, 80), dtype=torch.float32, device="cuda")
         self.d_emb = torch.empty((self.cap, self.emb.dim), dtype=torch.float32, device="cuda")
         self.s_campp = torch.cuda.Stream()
@@ -297,6 +320,8 @@ class FullPipe:
                            "windows": win,
                            "token_ids": [r.token_ids.tolist()
                                          for r in res_all[p * n:(p + 1) * n]]}
+                    if self.overlap_regions is not None:
+                        out["overlap_regions"] = list(self.overlap_regions)
                     if self.diar is not None:
                         out["speaker_segments"], out["speaker_labels"] = self.speakers(embs, win)
                     outs.append(out)
