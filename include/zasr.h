@@ -567,6 +567,43 @@ int zasr_selftest_bias_norm(int32_t rows, int32_t d, const float* bias, float lo
    if it exceeds cap. */
 int zasr_selftest_attn_block_map(const int32_t* lens, int32_t nseq, int32_t units_per_seq,
                                  int32_t order, uint32_t* out, int64_t cap, int32_t* grid);
+/* The attention kernels alone on one ragged batch of host operands (same conventions as the
+   convolution entries; no reference counterpart: test infrastructure).  L[nseq] frames per
+   sequence (0 allowed, at least one frame in all), R = sum L packed rows.  qkp [R][68 H]: per row
+   the queries [H][32], the keys [H][32], the positional queries [H][4]; pos_tab
+   [2 pmax - 1][4 H], row x + pmax - 1 for the key offset x = j - i.  mode: ZASR_PRECISION_FP32
+   (attn_softmax_kernel / attn_sa_kernel) or _BF16, _BF16X3, _BF16X6, _F16X3 (attn_flash_kernel
+   through launch_attn_flash with the block map in the decode's order).  In the bf16 mode qkp, v,
+   h3, out and z are held in bf16 on the device (rounded to nearest even on upload, widened on
+   return) and the stored query and positional-query columns carry the log2(e) factor the model
+   loader folds into attn_in, so the softmax is taken in base 2 over the stored values; the
+   other modes take the natural softmax.  Offsets are those a decode derives (the weight block
+   of sequence b is [L_b][stride], stride = L_b rounded up to 32, to 4 in fp32; t1^T columns
+   32-padded per sequence).  Every output holds its buffer's initial contents on entry; a guard
+   region follows each on the device and a changed guard byte returns ZASR_ERR_RUNTIME.  Refused
+   with ZASR_ERR_RUNTIME before any launch: an odd H or H > 16 outside fp32, a negative length,
+   pmax below the longest sequence (fp32: below that length rounded up to 32, its kernels do not
+   clamp the table rows), hid % 4 != 0, and a mode the entry's route does not have.
+   attn_weights: head 0's normalised weights as a decode materialises them, A0 [sum L_b
+   stride_b] f32, padding columns zero; modes fp32, bf16x3, bf16x6 (bf16 and f16x3 consume the
+   weights inside the fused NonlinAttention kernel: refused).
+   attn_sa: the layer's two self-attentions, out1 = softmax(S) v1 with running statistics
+   (flash mode 1 / attn_sa online), which writes stats, then out2 = softmax(S) v2 from those
+   stored statistics (flash mode 2 / attn_sa); v, out [R][12 H]; stats [R][H], row max +
+   log2(row sum) of the base-2 scores (fp32: [R][H][2], row max and 1 / row sum, natural).
+   nonlin: h3 [R][3 hid] = (s, x, y); t1t receives launch_nonlin_prep_t's image of
+   t1 = tanh(s) x as stored: [pieces][hid][sum L32_b] 16-bit patterns (bf16: one bf16 plane;
+   bf16x3 / bf16x6: 2 / 3 bf16 planes that sum to t1; f16x3: the fp16 planes hi and
+   (t1 - hi) 2^11).  bf16 and f16x3 then run flash mode 3, z [R][hid] = (A0 t1) y; bf16x3 /
+   bf16x6 stop at the image (z may be null); fp32 is refused. */
+int zasr_selftest_attn_weights(int32_t mode, int32_t H, int32_t nseq, const int32_t* L,
+                               int32_t pmax, const float* qkp, const float* pos_tab, float* A0);
+int zasr_selftest_attn_sa(int32_t mode, int32_t H, int32_t nseq, const int32_t* L, int32_t pmax,
+                          const float* qkp, const float* pos_tab, const float* v1,
+                          const float* v2, float* out1, float* stats, float* out2);
+int zasr_selftest_nonlin(int32_t mode, int32_t H, int32_t nseq, const int32_t* L, int32_t pmax,
+                         int32_t hid, const float* qkp, const float* pos_tab, const float* h3,
+                         uint16_t* t1t, float* z);
 
 /* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
    core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the

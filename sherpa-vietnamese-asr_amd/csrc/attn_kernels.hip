@@ -893,11 +893,17 @@ __global__ __launch_bounds__(256) void nonlin_prep_t_kernel(const TH* __restrict
   for (int k = 0; k < 4; ++k) {
     const int idx = tid + 256 * k;
     const int rl = idx >> 4, c4 = idx & 15;
-    const float m = sRow[rl] < 0 ? 0.f : 1.f;  // padding columns: zeros
-    tile[4 * c4 + 0][rl] = tanhf(sv[k].x) * xv[k].x * m;
-    tile[4 * c4 + 1][rl] = tanhf(sv[k].y) * xv[k].y * m;
-    tile[4 * c4 + 2][rl] = tanhf(sv[k].z) * xv[k].z * m;
-    tile[4 * c4 + 3][rl] = tanhf(sv[k].w) * xv[k].w * m;
+    // padding columns: +0 by masking the bits, one v_and where the product times 0 took one
+    // v_mul (that zero carried the sign of the re-read row's product, so a sequence's image
+    // depended on its neighbours, and a non-finite value in that row reached the padding)
+    const unsigned keep = sRow[rl] < 0 ? 0u : ~0u;
+    auto put = [keep](float v) {
+      return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & keep);
+    };
+    tile[4 * c4 + 0][rl] = put(tanhf(sv[k].x) * xv[k].x);
+    tile[4 * c4 + 1][rl] = put(tanhf(sv[k].y) * xv[k].y);
+    tile[4 * c4 + 2][rl] = put(tanhf(sv[k].z) * xv[k].z);
+    tile[4 * c4 + 3][rl] = put(tanhf(sv[k].w) * xv[k].w);
   }
   __syncthreads();
   // channel cl, columns 16 g .. 16 g + 15: reads tile row cl (stride 65: conflict-free)

@@ -1167,7 +1167,7 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(AttnArgs a) {
     f32x16 acc;
     scores(kb * 32, acc);
     const int j = kb * 32 + col;
-    if (j >= L) continue;
+    if (j >= lda) continue;  // columns [L, lda): exp(-inf) = 0, the row padding written as zeros
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = (r & 3) + 8 * (r >> 2) + 4 * hl;

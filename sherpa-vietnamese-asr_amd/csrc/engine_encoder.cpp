@@ -144,7 +144,8 @@ void Engine::self_attention(const StackCtx& c, const DLayer& Ly, int k, float* X
   const int d = c.stk->d, h = c.stk->h, R = c.R;
   const bool h16 = prec_.bf16_act;
   const size_t n = (size_t)R * 12 * h;
-  void* vv = h16 ? (void*)ws<__bf16>("ly_vv_h", n) : (void*)ws<float>("ly_vv", n);
+  // (bf16: the flash kernels' V staging reads 4 elements past the last row, kernels.h)
+  void* vv = h16 ? (void*)ws<__bf16>("ly_vv_h", n + 4) : (void*)ws<float>("ly_vv", n);
   void* oa = h16 ? (void*)ws<__bf16>("ly_oa_h", n) : (void*)ws<float>("ly_oa", n);
   project(Ly.sa_in[k], X, false, d, R, vv, h16, 12 * h, EPI_NONE);
   prof_begin("attn_apply");
@@ -380,30 +381,27 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
     for (int b = 0; b < B; ++b) len[b] = (L[b] + s.ds - 1) / s.ds;
     mst[i] = make_level(len);
     maxL_all = std::max(maxL_all, mst[i].maxlen);
-    long acc = 0;
     const int hid = 3 * s.d / 4;
-    int c8 = 0;
+    // head 0's weight blocks and the t1^T columns (kernels.h attn_head0_layout, which the
+    // attention self-tests share)
+    AttnHead0Layout lay = attn_head0_layout(len.data(), B, flash);
     for (int b = 0; b < B; ++b) {
-      const int Lb = len[b], L4 = (Lb + 3) & ~3, L8 = (Lb + 31) & ~31;
-      // weight row stride (flash: the GEMM's K padding, 32 for the LDS-DMA nonlin GEMM)
-      const int Lp = flash ? L8 : L4;
-      aoff[i].push_back(acc);
-      o8[i].push_back(c8);
+      const int Lb = len[b], L8 = (Lb + 31) & ~31;
       GemmSlice g{};
-      g.a_off = acc;  // head 0 block of this sequence
-      g.b_off = flash ? (long)c8 : (long)mst[i].off[b] * hid;  // flash: column of t1^T
+      g.a_off = lay.a_off[b];  // head 0 block of this sequence
+      g.b_off = flash ? (long)lay.o32[b] : (long)mst[i].off[b] * hid;  // flash: column of t1^T
       g.c_off = (long)mst[i].off[b] * hid;
       g.aux_off = (long)mst[i].off[b] * 3 * hid;
       g.M = Lb;
       g.K = flash ? L8 : Lb;
-      g.lda = Lp;
+      // weight row stride (flash: the GEMM's K padding, 32 for the LDS-DMA nonlin GEMM)
+      g.lda = AttnHead0Layout::stride(Lb, flash);
       sl_nl[i].push_back(g);
-      acc += (long)Lb * Lp;  // only head 0 is materialised (nonlin_attention)
-      c8 += L8;
     }
-    o8[i].push_back(c8);
-    R8[i] = c8;
-    attn_floats = std::max(attn_floats, (size_t)acc);
+    R8[i] = lay.R32;
+    attn_floats = std::max(attn_floats, lay.elems);
+    aoff[i] = std::move(lay.a_off);
+    o8[i] = std::move(lay.o32);
   }
   ensure_pos_tables(maxL_all + 192);  // the bf16 attention stages rows up to L + 160
   // frontend conv slices

@@ -265,6 +265,16 @@ void selftest_convnext(int nseq, const int* L, int form, const float* x, const f
                        const float* b2, float* y, float* out);
 void selftest_bias_norm(int rows, int d, const float* bias, float log_scale, float* orig,
                         const float* bscale, int copy_mode, float* x, float* copy_out);
+// the attention kernels alone on host operands (selftest.cpp; zasr_selftest_attn_weights /
+// _attn_sa / _nonlin): offsets from attn_head0_layout, the block maps in the engine's order 0,
+// the launchers a decode calls, a guard region behind every output
+void selftest_attn_weights(int mode, int H, int nseq, const int* L, int pmax, const float* qkp,
+                           const float* pos_tab, float* A0);
+void selftest_attn_sa(int mode, int H, int nseq, const int* L, int pmax, const float* qkp,
+                      const float* pos_tab, const float* v1, const float* v2, float* out1,
+                      float* stats, float* out2);
+void selftest_nonlin(int mode, int H, int nseq, const int* L, int pmax, int hid, const float* qkp,
+                     const float* pos_tab, const float* h3, unsigned short* t1t, float* z);
 // row -> sequence index map for one resolution (off: [nseq + 1])
 void launch_row2seq(const int* off, int nseq, int total, int* map, hipStream_t st);
 // dst[r][0:dd] = src[r][0:min(ds, dd)], zero-padded  (convert_num_channels)
@@ -289,8 +299,9 @@ void launch_attn_softmax(const AttnArgs& a, hipStream_t st);
 // bf16 mode, flash-style attention (attn_kernels.hip): qkp / v / out in bf16; the query
 // and positional-query columns of qkp carry a log2(e) factor (folded into attn_in's bf16
 // weights and bias at load).
-//   mode 0: head-0 normalised weights in bf16, [L][L8] per sequence at a_off[b] (columns
-//           [L, L8) zero; L8 = L rounded up to 8), the NonlinAttention GEMM operand
+//   mode 0: head-0 normalised weights, [L][L32] per sequence at a_off[b] (L32 = L rounded up
+//           to 32, the key blocks the kernel walks; columns [L, L32) zero), the NonlinAttention
+//           GEMM operand (attn_head0_layout below)
 //   mode 1: self-attention with running statistics; writes out and stats_out
 //   mode 2: self-attention with the statistics of mode 1 (stats_in)
 //   mode 3: NonlinAttention fused, one online pass over head 0: running max / sum, the
@@ -299,6 +310,11 @@ void launch_attn_softmax(const AttnArgs& a, hipStream_t st);
 //           (pieces == kPiecesF16: fp16 pieces of the weights and of t1, one-accumulator
 //           products, f32 y / z)
 // stats: [R][H] c = row max + log2(row sum), log2 domain
+// Read contract: every operand is read inside its stated extent except v in the bf16 mode
+// (pieces == 1, modes 1 / 2): a V-staging thread loads 16 bytes (8 elements) of which it keeps
+// 4, so the load of the last row's last head ends 8 bytes past [R][12 H] -- v must be readable
+// for 4 more bf16 elements.  pos_tab rows are clamped to [0, 2 pmax - 2], so any pmax >= the
+// longest sequence serves (the rows a live score uses are then unclamped).
 struct AttnFlashArgs {
   const void* qkp;         // [R][68 H]: bf16 (pieces == 1) or f32
   int H;
@@ -308,8 +324,8 @@ struct AttnFlashArgs {
   const long* a_off;       // [B] (mode 0)
   int nseq;
   int max_len;
-  void* attn;              // mode 0: head 0's weights [L][L8] per sequence, bf16 / f32
-  const void* v;           // [R][12 H], bf16 / f32
+  void* attn;              // mode 0: head 0's weights [L][L32] per sequence, bf16 / f32
+  const void* v;           // [R][12 H], bf16 / f32 (bf16: + 4 readable elements, see above)
   void* out;               // [R][12 H], bf16 / f32
   const float* stats_in;   // mode 2
   float* stats_out;        // mode 1
@@ -336,6 +352,34 @@ struct AttnFlashArgs {
   int map_len = 0;
 };
 void launch_attn_flash(const AttnFlashArgs& a, int mode, hipStream_t st);
+// Where head 0's weights and NonlinAttention's t1^T columns of one ragged level lie (host): the
+// weight block of sequence b, [L_b][stride(L_b)], starts at element a_off[b]; the row stride is
+// L rounded up to 32 on the flash routes (the GEMM's K padding and the kernel's key blocks), to
+// 4 in the fp32 mode.  o32[b] is the first t1^T column of sequence b ([B + 1], 32-padded
+// lengths summed; the engine's "o8"), R32 = o32[B] the t1^T row stride, elems the size of
+// the weight buffer.
+struct AttnHead0Layout {
+  std::vector<long> a_off;
+  std::vector<int> o32;
+  int R32 = 0;
+  size_t elems = 0;
+  static int stride(int L, bool flash) { return flash ? (L + 31) & ~31 : (L + 3) & ~3; }
+};
+inline AttnHead0Layout attn_head0_layout(const int* len, int nseq, bool flash) {
+  AttnHead0Layout y;
+  long acc = 0;
+  int c32 = 0;
+  for (int b = 0; b < nseq; ++b) {
+    y.a_off.push_back(acc);
+    y.o32.push_back(c32);
+    acc += (long)len[b] * AttnHead0Layout::stride(len[b], flash);  // only head 0 is materialised
+    c32 += (len[b] + 31) & ~31;
+  }
+  y.o32.push_back(c32);
+  y.R32 = c32;
+  y.elems = (size_t)acc;
+  return y;
+}
 // mode 3: value fragments (32 rows of t1^T) per block and the z-chunks of hid they make.  bf16:
 // 5 fragments for hid = 144 (one chunk) and 288 (two), 6 for 192 (one) and 384 (two); f16x3
 // (two accumulators and two V^T images per fragment): 3 per block
@@ -373,7 +417,8 @@ struct AttnBlockMaps {
 int build_attn_block_map(const int* lens, int nseq, int units_per_seq, int order,
                          std::vector<unsigned>& map);
 // t1t[c][o8_b + j] = bf16(tanh(h3[r][c]) * h3[r][hid + c]) for packed row r = off_b + j;
-// columns [o8_b + L_b, o8_b + L8_b) zero; t1t row stride R8 = sum_b L8_b
+// columns [o8_b + L_b, o8_b + L32_b) +0; t1t row stride R8 = sum_b L32_b ("o8" / "R8": the
+// 32-padded attn_head0_layout o32 / R32)
 // pieces > 1 (an f32 h3, the split modes): piece t of every value at t1t + t * hid * R8
 void launch_nonlin_prep_t(const void* h3, bool h3_bf16, const int* off, const int* o8,
                           const int* map, int R, int hid, int R8, void* t1t, hipStream_t st,

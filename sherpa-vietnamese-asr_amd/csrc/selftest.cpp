@@ -589,4 +589,237 @@ void selftest_joiner(int mode, int layout, int M, int V, int D, const float* J, 
   o.down(out, "joiner");
 }
 
+// ---- the attention kernels ----
+namespace {
+constexpr size_t kAttnGuard = 1024;  // guard bytes behind every attention output
+
+// an output of `bytes` bytes that starts as the caller's image, kAttnGuard guard bytes behind it
+struct GuardedOut {
+  size_t bytes;
+  DevBuf d;
+  GuardedOut(const void* init, size_t bytes_) : bytes(bytes_), d(bytes_ + kAttnGuard) {
+    up(d, init, bytes);
+    ZASR_HIP_CHECK(hipMemset(d.as<unsigned char>() + bytes, 0x5a, kAttnGuard));
+  }
+  void down(void* out, const char* what) const {
+    unsigned char guard[kAttnGuard];
+    ZASR_HIP_CHECK(hipMemcpy(guard, d.as<unsigned char>() + bytes, kAttnGuard, hipMemcpyDeviceToHost));
+    for (unsigned char g : guard)
+      ZASR_REQUIRE(g == 0x5a, std::string("selftest ") + what + ": the kernel wrote past its output");
+    if (bytes) ZASR_HIP_CHECK(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));
+  }
+};
+// the same for an output the mode stores in f32 or in bf16 (rounded on upload, widened on return)
+struct GuardedOut16 {
+  size_t n;
+  bool h16;
+  std::unique_ptr<GuardedOut> g;
+  GuardedOut16(const float* init, size_t n_, bool h16_) : n(n_), h16(h16_) {
+    if (h16) g.reset(new GuardedOut(round16(init, n).data(), n * 2));
+    else g.reset(new GuardedOut(init, n * 4));
+  }
+  void* p() const { return g->d.p; }
+  void down(float* out, const char* what) const {
+    if (!h16) return g->down(out, what);
+    std::vector<__bf16> h(n);
+    g->down(h.data(), what);
+    for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
+  }
+};
+
+// one ragged attention problem on the device as a decode prepares it: the packed-row offsets,
+// head 0's weight offsets and the t1^T columns (attn_head0_layout), qkp [R][68 H] and the
+// positional table [2 pmax - 1][4 H].  Every shape the kernels cannot take is refused here,
+// before anything is launched.
+struct AttnProblem {
+  bool f32, h16, flash;
+  int pieces, H, nseq, pmax, R = 0, maxL = 0;
+  std::vector<int> len, off;
+  AttnHead0Layout lay;
+  std::unique_ptr<DevBuf> d_off, d_aoff, d_o32, d_qkp, d_pos, d_map;
+
+  AttnProblem(const char* what, int mode, int H_, int nseq_, const int* L, int pmax_,
+              const float* qkp, const float* pos_tab)
+      : H(H_), nseq(nseq_), pmax(pmax_) {
+    const std::string w = std::string("selftest ") + what + ": ";
+    f32 = mode == ZASR_PRECISION_FP32;
+    h16 = mode == ZASR_PRECISION_BF16;
+    pieces = mode == ZASR_PRECISION_BF16X3   ? 2
+             : mode == ZASR_PRECISION_BF16X6 ? 3
+             : mode == ZASR_PRECISION_F16X3  ? kPiecesF16
+                                             : 0;
+    flash = !f32;
+    ZASR_REQUIRE(f32 || h16 || pieces != 0,
+                 w + "mode must be ZASR_PRECISION_FP32, _BF16, _BF16X3, _BF16X6 or _F16X3");
+    ZASR_REQUIRE(nseq >= 1 && nseq <= kAttnMapMaxSeq && L != nullptr, w + "at least one sequence");
+    ZASR_REQUIRE(H >= 1 && (!flash || (H % 2 == 0 && H <= kAttnMapMaxUnits)),
+                 w + "the flash kernels take an even head count of at most 16");
+    off.assign(nseq + 1, 0);
+    for (int b = 0; b < nseq; ++b) {
+      ZASR_REQUIRE(L[b] >= 0 && L[b] <= 128 * kAttnMapMaxTiles, w + "sequence length out of range");
+      len.push_back(L[b]);
+      off[b + 1] = off[b] + L[b];
+      maxL = std::max(maxL, L[b]);
+    }
+    R = off[nseq];
+    ZASR_REQUIRE(R >= 1, w + "at least one frame");
+    // the flash kernels clamp the positional rows; the fp32 kernels read rows j - i for every
+    // (query, key) of their 32 x 32 tiles unclamped, |j - i| < max(L) rounded up to 32
+    ZASR_REQUIRE(pmax >= (flash ? maxL : (maxL + 31) / 32 * 32),
+                 w + "pmax below the longest sequence (fp32: rounded up to 32)");
+    lay = attn_head0_layout(len.data(), nseq, flash);
+    const size_t nq = (size_t)R * 68 * H, np = (size_t)(2 * pmax - 1) * 4 * H;
+    d_off.reset(new DevBuf(off.size() * 4));
+    d_aoff.reset(new DevBuf(lay.a_off.size() * sizeof(long)));
+    d_o32.reset(new DevBuf(lay.o32.size() * 4));
+    d_qkp.reset(new DevBuf(nq * (h16 ? 2 : 4)));
+    d_pos.reset(new DevBuf(np * 4));
+    d_map.reset(new DevBuf((size_t)R * 4));
+    up(*d_off, off.data(), off.size() * 4);
+    up(*d_aoff, lay.a_off.data(), lay.a_off.size() * sizeof(long));
+    up(*d_o32, lay.o32.data(), lay.o32.size() * 4);
+    up16(*d_qkp, qkp, nq, h16);
+    up(*d_pos, pos_tab, np * 4);
+  }
+  // the flash arguments the engine's attention_weights forms
+  AttnFlashArgs flash_args() const {
+    AttnFlashArgs a{};
+    a.qkp = d_qkp->p;
+    a.H = H;
+    a.pos_tab = d_pos->as<float>();
+    a.pmax = pmax;
+    a.row_off = d_off->as<int>();
+    a.a_off = d_aoff->as<long>();
+    a.nseq = nseq;
+    a.max_len = maxL;
+    a.pieces = h16 ? 1 : pieces;
+    return a;
+  }
+};
+
+// one block map in the engine's order 0, on the device
+struct AttnMap {
+  std::vector<unsigned> host;
+  int n;
+  DevBuf d;
+  static std::vector<unsigned> make(const std::vector<int>& len, int units) {
+    std::vector<unsigned> m;
+    build_attn_block_map(len.data(), (int)len.size(), units, 0, m);
+    return m;
+  }
+  AttnMap(const std::vector<int>& len, int units)
+      : host(make(len, units)), n((int)host.size()), d(host.size() * 4) {
+    up(d, host.data(), host.size() * 4);
+  }
+};
+}  // namespace
+
+void selftest_attn_weights(int mode, int H, int nseq, const int* L, int pmax, const float* qkp,
+                           const float* pos_tab, float* A0) {
+  AttnProblem c("attn_weights", mode, H, nseq, L, pmax, qkp, pos_tab);
+  ZASR_REQUIRE(c.f32 || c.pieces == 2 || c.pieces == 3,
+               "selftest attn_weights: head 0's weights are materialised in the fp32, bf16x3 and "
+               "bf16x6 modes only (bf16 and f16x3 consume them inside flash mode 3)");
+  GuardedOut o(A0, c.lay.elems * 4);
+  if (c.f32) {
+    GuardedOut st(std::vector<float>((size_t)c.R * H * 2, 0.f).data(), (size_t)c.R * H * 2 * 4);
+    AttnArgs a{c.d_qkp->as<float>(), H, c.d_pos->as<float>(), pmax, c.d_off->as<int>(),
+               c.d_aoff->as<long>(), nseq, c.maxL, o.d.as<float>(), st.d.as<float>(), 1};
+    launch_attn_softmax(a, nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<float> sink((size_t)c.R * H * 2);
+    st.down(sink.data(), "attn_weights");
+  } else {
+    const AttnMap m(c.len, 1);
+    AttnFlashArgs a = c.flash_args();
+    a.attn = o.d.p;
+    a.map = m.d.as<unsigned>();
+    a.map_len = m.n;
+    launch_attn_flash(a, 0, nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+  }
+  o.down(A0, "attn_weights");
+}
+
+void selftest_attn_sa(int mode, int H, int nseq, const int* L, int pmax, const float* qkp,
+                      const float* pos_tab, const float* v1, const float* v2, float* out1,
+                      float* stats, float* out2) {
+  AttnProblem c("attn_sa", mode, H, nseq, L, pmax, qkp, pos_tab);
+  const size_t n = (size_t)c.R * 12 * H, ns = (size_t)c.R * H * (c.f32 ? 2 : 1);
+  // bf16: 4 readable elements behind v, the flash kernels' read contract (kernels.h)
+  const size_t vb = c.h16 ? (n + 4) * 2 : n * 4;
+  DevBuf dv1(vb), dv2(vb);
+  ZASR_HIP_CHECK(hipMemset(dv1.p, 0, vb));
+  ZASR_HIP_CHECK(hipMemset(dv2.p, 0, vb));
+  up16(dv1, v1, n, c.h16);
+  up16(dv2, v2, n, c.h16);
+  GuardedOut16 o1(out1, n, c.h16), o2(out2, n, c.h16);
+  GuardedOut st(stats, ns * 4);
+  if (c.flash) {
+    const AttnMap m(c.len, H);
+    AttnFlashArgs a = c.flash_args();
+    a.map = m.d.as<unsigned>();
+    a.map_len = m.n;
+    a.stats_in = st.d.as<float>();
+    a.stats_out = st.d.as<float>();
+    a.v = dv1.p;
+    a.out = o1.p();
+    launch_attn_flash(a, 1, nullptr);
+    a.v = dv2.p;
+    a.out = o2.p();
+    launch_attn_flash(a, 2, nullptr);
+  } else {
+    AttnSAArgs sa{c.d_qkp->as<float>(), H, c.d_pos->as<float>(), pmax, c.d_off->as<int>(), nseq,
+                  c.maxL, st.d.as<float>(), dv1.as<float>(), reinterpret_cast<float*>(o1.p()),
+                  st.d.as<float>()};
+    launch_attn_sa(sa, true, false, nullptr);
+    sa.v = dv2.as<float>();
+    sa.out = reinterpret_cast<float*>(o2.p());
+    launch_attn_sa(sa, false, false, nullptr);
+  }
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o1.down(out1, "attn_sa");
+  st.down(stats, "attn_sa");
+  o2.down(out2, "attn_sa");
+}
+
+void selftest_nonlin(int mode, int H, int nseq, const int* L, int pmax, int hid, const float* qkp,
+                     const float* pos_tab, const float* h3, unsigned short* t1t, float* z) {
+  AttnProblem c("nonlin", mode, H, nseq, L, pmax, qkp, pos_tab);
+  ZASR_REQUIRE(!c.f32, "selftest nonlin: the fp32 route (row-major t1) is not covered");
+  ZASR_REQUIRE(hid >= 4 && hid % 4 == 0, "selftest nonlin: hid a positive multiple of 4");
+  const bool fused = c.h16 || c.pieces == kPiecesF16;  // flash mode 3 follows the transpose
+  ZASR_REQUIRE(!fused || z != nullptr, "selftest nonlin: z");
+  const int np = c.h16 ? 1 : c.pieces, R32 = c.lay.R32;
+  const size_t nh = (size_t)c.R * 3 * hid, nt = (size_t)stored_pieces(np) * hid * R32,
+               nz = (size_t)c.R * hid;
+  DevBuf dh(nh * (c.h16 ? 2 : 4));
+  up16(dh, h3, nh, c.h16);
+  launch_row2seq(c.d_off->as<int>(), nseq, c.R, c.d_map->as<int>(), nullptr);
+  GuardedOut ot(t1t, nt * 2);
+  launch_nonlin_prep_t(dh.p, c.h16, c.d_off->as<int>(), c.d_o32->as<int>(), c.d_map->as<int>(), c.R,
+                       hid, R32, ot.d.p, nullptr, np);
+  if (!fused) {
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    ot.down(t1t, "nonlin");
+    return;
+  }
+  GuardedOut16 oz(z, nz, c.h16);
+  const AttnMap m(c.len, attn_nonlin_chunks(hid, np));
+  AttnFlashArgs a = c.flash_args();
+  a.t1t = ot.d.p;
+  a.o8 = c.d_o32->as<int>();
+  a.ldt = R32;
+  a.hid = hid;
+  a.y = c.h16 ? (const void*)(dh.as<__bf16>() + 2 * hid) : (const void*)(dh.as<float>() + 2 * hid);
+  a.ldy = 3 * hid;
+  a.z = oz.p();
+  a.map = m.d.as<unsigned>();
+  a.map_len = m.n;
+  launch_attn_flash(a, 3, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  ot.down(t1t, "nonlin");
+  oz.down(z, "nonlin");
+}
+
 }  // namespace zasr

@@ -810,6 +810,36 @@ int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int
   });
 }
 
+int zasr_selftest_attn_weights(int32_t mode, int32_t H, int32_t nseq, const int32_t* L,
+                               int32_t pmax, const float* qkp, const float* pos_tab, float* A0) {
+  if (!L || !qkp || !pos_tab || !A0) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_attn_weights(mode, H, nseq, L, pmax, qkp, pos_tab, A0);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_attn_sa(int32_t mode, int32_t H, int32_t nseq, const int32_t* L, int32_t pmax,
+                          const float* qkp, const float* pos_tab, const float* v1,
+                          const float* v2, float* out1, float* stats, float* out2) {
+  if (!L || !qkp || !pos_tab || !v1 || !v2 || !out1 || !stats || !out2)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_attn_sa(mode, H, nseq, L, pmax, qkp, pos_tab, v1, v2, out1, stats, out2);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_nonlin(int32_t mode, int32_t H, int32_t nseq, const int32_t* L, int32_t pmax,
+                         int32_t hid, const float* qkp, const float* pos_tab, const float* h3,
+                         uint16_t* t1t, float* z) {
+  if (!L || !qkp || !pos_tab || !h3 || !t1t) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_nonlin(mode, H, nseq, L, pmax, hid, qkp, pos_tab, h3, t1t, z);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const float* W1,
                          const float* b1, const float* W2, const float* b2,
                          const float* byp_orig, const float* byp_scale, float* X) {

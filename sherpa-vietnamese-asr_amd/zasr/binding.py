@@ -42,7 +42,8 @@ EXPORTS = (
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
     "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm", "zasr_selftest_joiner",
     "zasr_selftest_dwconv1d", "zasr_selftest_conv1", "zasr_selftest_convnext",
-    "zasr_selftest_bias_norm",
+    "zasr_selftest_bias_norm", "zasr_selftest_attn_weights", "zasr_selftest_attn_sa",
+    "zasr_selftest_nonlin",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -274,6 +275,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_convnext.restype = C.c_int
     lib.zasr_selftest_bias_norm.argtypes = [I32, I32, fp, C.c_float, fp, fp, I32, fp, fp]
     lib.zasr_selftest_bias_norm.restype = C.c_int
+    lib.zasr_selftest_attn_weights.argtypes = [I32] * 3 + [C.POINTER(I32), I32] + [fp] * 3
+    lib.zasr_selftest_attn_weights.restype = C.c_int
+    lib.zasr_selftest_attn_sa.argtypes = [I32] * 3 + [C.POINTER(I32), I32] + [fp] * 7
+    lib.zasr_selftest_attn_sa.restype = C.c_int
+    lib.zasr_selftest_nonlin.argtypes = [I32] * 3 + [C.POINTER(I32), I32, I32] + [fp] * 3 + [
+        C.POINTER(C.c_uint16), fp]
+    lib.zasr_selftest_nonlin.restype = C.c_int
     # device audio front end (zasr/audio.py)
     lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
     lib.zasr_audio_create.restype = C.c_int
@@ -528,6 +536,82 @@ def selftest_dwconv1d(L, x, w, b, glu: bool, bf16: bool = False, fill: float = -
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return out
+
+
+def _attn_operands(L, H, pmax, qkp, pos_tab):
+    L, qkp, pos_tab = _lens(L), _f32(qkp), _f32(pos_tab)
+    rows = int(L.sum()) if L.size and L.min() >= 0 else -1
+    if rows >= 0:  # (a negative length goes to the entry, which refuses it)
+        assert qkp.shape == (rows, 68 * H) and pos_tab.shape == (2 * pmax - 1, 4 * H)
+    return L, qkp, pos_tab, rows
+
+
+def attn_head0_strides(L, mode: str) -> np.ndarray:
+    """Row stride of each sequence's head-0 weight block: L rounded up to 32 (4 in fp32)."""
+    L = np.asarray(L, dtype=np.int64)
+    return (L + 3) // 4 * 4 if mode == "fp32" else (L + 31) // 32 * 32
+
+
+def selftest_attn_weights(mode: str, H: int, L, pmax: int, qkp, pos_tab, fill: float = -777.25,
+                          lib_path: Optional[str] = None) -> np.ndarray:
+    """Head 0's normalised attention weights as a decode materialises them
+    (zasr_selftest_attn_weights): the flat buffer of the per-sequence [L][stride] blocks
+    (attn_head0_strides), which started as `fill`."""
+    lib = load_library(lib_path)
+    L, qkp, pos_tab, _ = _attn_operands(L, H, pmax, qkp, pos_tab)
+    n = int((np.maximum(L, 0).astype(np.int64) * attn_head0_strides(np.maximum(L, 0), mode)).sum())
+    A0 = np.full(max(n, 1), fill, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_attn_weights(PRECISIONS[mode], int(H), len(L),
+                                        L.ctypes.data_as(C.POINTER(C.c_int32)), int(pmax), p(qkp),
+                                        p(pos_tab), p(A0))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return A0[:n]
+
+
+def selftest_attn_sa(mode: str, H: int, L, pmax: int, qkp, pos_tab, v1, v2, fill: float = -777.25,
+                     lib_path: Optional[str] = None):
+    """A layer's two self-attentions alone (zasr_selftest_attn_sa): returns (out1 [R][12 H] from
+    running statistics on v1, stats [R][H] (fp32: [R][H][2]), out2 from those statistics on
+    v2); every output started as `fill`."""
+    lib = load_library(lib_path)
+    L, qkp, pos_tab, rows = _attn_operands(L, H, pmax, qkp, pos_tab)
+    v1, v2 = _f32(v1), _f32(v2)
+    rows = max(rows, 0)
+    out1 = np.full((rows, 12 * H), fill, dtype=np.float32)
+    out2 = out1.copy()
+    stats = np.full((rows, H, 2) if mode == "fp32" else (rows, H), fill, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_attn_sa(PRECISIONS[mode], int(H), len(L),
+                                   L.ctypes.data_as(C.POINTER(C.c_int32)), int(pmax), p(qkp),
+                                   p(pos_tab), p(v1), p(v2), p(out1), p(stats), p(out2))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out1, stats, out2
+
+
+def selftest_nonlin(mode: str, H: int, L, pmax: int, hid: int, qkp, pos_tab, h3,
+                    fill: float = -777.25, lib_path: Optional[str] = None):
+    """NonlinAttention's kernels alone (zasr_selftest_nonlin): returns (t1t
+    [pieces][hid][sum L32] uint16 as stored, which started as 0x7e7e; z [R][hid], which started
+    as `fill`, or None in bf16x3 / bf16x6 where the route stops at the image)."""
+    lib = load_library(lib_path)
+    L, qkp, pos_tab, rows = _attn_operands(L, H, pmax, qkp, pos_tab)
+    h3 = _f32(h3)
+    rows = max(rows, 0)
+    planes = {"bf16": 1, "bf16x3": 2, "bf16x6": 3, "f16x3": 2}.get(mode, 1)
+    r32 = int(((np.maximum(L, 0) + 31) // 32 * 32).sum())
+    t1t = np.full((planes, max(hid, 0), r32), 0x7e7e, dtype=np.uint16)
+    z = np.full((rows, max(hid, 0)), fill, dtype=np.float32) if mode in ("bf16", "f16x3") else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_nonlin(PRECISIONS[mode], int(H), len(L),
+                                  L.ctypes.data_as(C.POINTER(C.c_int32)), int(pmax), int(hid),
+                                  p(qkp), p(pos_tab), p(h3),
+                                  t1t.ctypes.data_as(C.POINTER(C.c_uint16)), p(z))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return t1t, z
 
 
 def selftest_conv1(T, fb, w, b, form: int, fill: float = -777.25,
