@@ -605,6 +605,79 @@ int zasr_selftest_nonlin(int32_t mode, int32_t H, int32_t nseq, const int32_t* L
                          int32_t hid, const float* qkp, const float* pos_tab, const float* h3,
                          uint16_t* t1t, float* z);
 
+/* The transducer search kernels alone on host arrays (no reference counterpart: test
+   infrastructure): one frame of launch_search_step, one super-step of launch_greedy_spec, and
+   launch_search_final, through the launchers a decode calls.  Every array is uploaded, the
+   call synchronises, and every array marked in / out is returned as the device holds it
+   afterwards; all arrays of a call sit in one device allocation with a guard region before and
+   behind each, and a changed guard byte returns ZASR_ERR_RUNTIME.  Every argument is checked
+   before anything is launched (ZASR_ERR_INVALID for a null argument, ZASR_ERR_RUNTIME with a
+   message otherwise).
+   zasr_st_state: the SearchState of S streams x Hmax hypothesis slots (kernels.h), all in / out:
+   lp, lpf, hash, len, y1, y2, hw, node [S Hmax], nh [S]; the emission node pool node_tok /
+   node_frame / node_parent / node_lp [S node_cap], node_stats [S node_cap][4], node_count [S].
+   hash is opaque: returned by one call and passed to the next.  Live slots (below nh) must hold
+   y1, y2 in [0, V), hw a state of the automaton, node in [-1, node_count); node_cap must leave
+   room for `beam` (greedy: 1) more nodes behind node_count in every stream.
+   zasr_st_hotwords: n phrases as concatenated token ids (lens[n]) with their scores; the
+   automaton is the engine's own build_hotword_dfa.  n = 0: no hotwords.
+   zasr_st_table: the decoder-context table and the joiner input it feeds.  The entry builds
+   the full table itself, table[y2][y1][:] = a[y2][:] + b[y1][:] (a, b [V][D]; V V D floats, at
+   most 2^27: a small D for the large vocabularies), so no context a kernel forms can index
+   outside it.  enc [enc_rows][D], stream s's frames from row enc_off[s] (enc_off[s] + enc_len[s]
+   <= enc_rows).  jfmt: 0 f32 [rows][D]; 1 bf16 [rows][D]; 2 bf16 in MFMA-fragment order
+   (kernels.h JoinerArgs, JOINER_PACKED; joiner_packed_rows(rows) rows); 3 / 4: 2 / 3 bf16 piece
+   images in fragment order; 5: the fp16 images hi and (x - hi) 2^11 in fragment order (2 - 5:
+   D = 256 or 512).  J (in / out, j_bytes = exactly the format's size) is returned whole.
+   search_step: t >= 0: one frame, logits [S Hmax][V] (every row readable); tab nullable (the
+   decjoin route's instantiation, no J).  t < 0: launch_search_init (and launch_table_init with a
+   table) instead, logits ignored.  J rows = S Hmax.
+   greedy_spec: beam 1 (Hmax = 1), window F = 4 or 8, logits [S][F][V], J rows = S F, t_cur [S]
+   and active [2] in / out.  init 0: the super-step; 1: launch_search_init +
+   launch_greedy_spec_init, then the super-step; 2: the two init launches alone.
+   search_final: out_tok / out_frame / out_lp [S out_cap], out_stats [S out_cap][4], out_count
+   [S], all in / out; node_parent[i] must be in [-1, i).
+   hotword_dfa: build_hotword_dfa's tables on the host (no launch): tok2cls [V]; with
+   *num_states and *num_cls set on return, next / delta [cap] and node_score [cap] receive
+   [states][cls] and [states] (ZASR_ERR_RUNTIME when cap is too small). */
+typedef struct zasr_st_state {
+  int32_t S, Hmax, node_cap;
+  double* lp;
+  int32_t* lpf;
+  uint64_t* hash;
+  int32_t *len, *y1, *y2, *hw, *node, *nh;
+  int32_t *node_tok, *node_frame, *node_parent;
+  double* node_lp;
+  float* node_stats;
+  int32_t* node_count;
+} zasr_st_state;
+typedef struct zasr_st_hotwords {
+  const int32_t* tokens;
+  const int32_t* lens;
+  const float* scores;
+  int32_t n;
+} zasr_st_hotwords;
+typedef struct zasr_st_table {
+  int32_t D, jfmt, enc_rows;
+  const float *a, *b, *enc;
+  const int32_t* enc_off;
+  void* J;
+  int64_t j_bytes;
+} zasr_st_table;
+int zasr_selftest_search_step(int32_t V, int32_t beam, int32_t t, const int32_t* enc_len,
+                              const zasr_st_state* st, const float* logits,
+                              const zasr_st_hotwords* hw, const zasr_st_table* tab);
+int zasr_selftest_greedy_spec(int32_t V, int32_t F, int32_t init, int32_t parity,
+                              const int32_t* enc_len, int32_t* t_cur, int32_t* active,
+                              const zasr_st_state* st, const float* logits,
+                              const zasr_st_hotwords* hw, const zasr_st_table* tab);
+int zasr_selftest_search_final(int32_t V, const zasr_st_state* st, const zasr_st_hotwords* hw,
+                               int32_t out_cap, int32_t* out_tok, int32_t* out_frame,
+                               double* out_lp, float* out_stats, int32_t* out_count);
+int zasr_selftest_hotword_dfa(int32_t V, const zasr_st_hotwords* hw, int32_t cap,
+                              int32_t* num_states, int32_t* num_cls, int32_t* tok2cls,
+                              int32_t* next, double* delta, double* node_score);
+
 /* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
    core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the
    eigenvectors; the eigengap rule, k-means and the segment logic are host code in

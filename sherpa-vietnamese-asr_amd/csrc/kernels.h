@@ -9,6 +9,10 @@
 
 #include <hip/hip_runtime.h>
 
+struct zasr_st_state;     // include/zasr.h: the search self-tests' host arrays
+struct zasr_st_hotwords;
+struct zasr_st_table;
+
 namespace zasr {
 
 // ---- fbank (core/asr_engine.py:698-721, kaldi semantics: SURVEY Appendix A) ----
@@ -275,6 +279,21 @@ void selftest_attn_sa(int mode, int H, int nseq, const int* L, int pmax, const f
                       float* stats, float* out2);
 void selftest_nonlin(int mode, int H, int nseq, const int* L, int pmax, int hid, const float* qkp,
                      const float* pos_tab, const float* h3, unsigned short* t1t, float* z);
+// the transducer search kernels alone on host arrays (selftest.cpp; zasr_selftest_search_step /
+// _greedy_spec / _search_final / _hotword_dfa, include/zasr.h): the launchers a decode calls on
+// the uploaded state, the hotword tables from build_hotword_dfa, the decoder-context table built
+// in full from two [V][D] arrays, guard regions around every array, every argument checked
+// before a launch
+void selftest_search_step(int V, int beam, int t, const int* enc_len, const zasr_st_state& st,
+                          const float* logits, const zasr_st_hotwords& hw, const zasr_st_table* tab);
+void selftest_greedy_spec(int V, int F, int init, int parity, const int* enc_len, int* t_cur,
+                          int* active, const zasr_st_state& st, const float* logits,
+                          const zasr_st_hotwords& hw, const zasr_st_table& tab);
+void selftest_search_final(int V, const zasr_st_state& st, const zasr_st_hotwords& hw, int out_cap,
+                           int* out_tok, int* out_frame, double* out_lp, float* out_stats,
+                           int* out_count);
+void selftest_hotword_dfa(int V, const zasr_st_hotwords& hw, int cap, int* num_states,
+                          int* num_cls, int* tok2cls, int* next, double* delta, double* node_score);
 // row -> sequence index map for one resolution (off: [nseq + 1])
 void launch_row2seq(const int* off, int nseq, int total, int* map, hipStream_t st);
 // dst[r][0:dd] = src[r][0:min(ds, dd)], zero-padded  (convert_num_channels)

@@ -5,8 +5,10 @@
 // host; the fused FFNs also out of place, the fused stack seam beside the kernels it
 // replaces, and the convolution path's hand-written kernels (ConvolutionModule depthwise conv,
 // conv.0, the ConvNeXt block) and BiasNorm on ragged batches given as per-sequence lengths, and
-// the joiner kernels on row-major and on host-packed J.
+// the joiner kernels on row-major and on host-packed J, and the transducer search kernels (one
+// frame, one greedy window, the final pick) on a caller-supplied search state.
 // Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -14,6 +16,7 @@
 #include "../../include/zasr.h"
 #include "common.h"
 #include "dense_gemm.h"
+#include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
 
@@ -820,6 +823,382 @@ void selftest_nonlin(int mode, int H, int nseq, const int* L, int pmax, int hid,
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   ot.down(t1t, "nonlin");
   oz.down(z, "nonlin");
+}
+
+// ---- the transducer search kernels ----
+namespace {
+constexpr size_t kSearchGuard = 256;  // guard bytes before the first and behind every array
+
+// every array of one call in one device allocation, one upload and one download: array i starts
+// 256-aligned, the bytes up to the next array (at least kSearchGuard) are guard bytes
+struct SearchArena {
+  struct Seg {
+    size_t off, bytes;
+    const void* src;
+    void* dst;  // null: an input
+  };
+  std::vector<Seg> segs;
+  size_t total = kSearchGuard;
+  std::unique_ptr<DevBuf> d;
+  size_t add(const void* src, size_t bytes, void* dst = nullptr) {
+    segs.push_back(Seg{total, bytes, src, dst});
+    total += (bytes + 255) / 256 * 256 + kSearchGuard;
+    return segs.size() - 1;
+  }
+  template <class T>
+  size_t io(T* p, size_t n) { return add(p, n * sizeof(T), p); }
+  template <class T>
+  size_t in(const T* p, size_t n) { return add(p, n * sizeof(T)); }
+  void upload() {
+    std::vector<unsigned char> img(total, 0x5a);
+    for (const Seg& g : segs)
+      if (g.bytes) std::memcpy(img.data() + g.off, g.src, g.bytes);
+    d.reset(new DevBuf(total));
+    up(*d, img.data(), total);
+  }
+  template <class T>
+  T* at(size_t i) const { return reinterpret_cast<T*>(d->as<unsigned char>() + segs[i].off); }
+  // the guard bytes intact, then every in / out array back to the caller
+  void download(const char* what) const {
+    std::vector<unsigned char> img(total);
+    ZASR_HIP_CHECK(hipMemcpy(img.data(), d->p, total, hipMemcpyDeviceToHost));
+    size_t pos = 0;
+    for (size_t i = 0; i <= segs.size(); ++i) {
+      const size_t end = i < segs.size() ? segs[i].off : total;
+      for (; pos < end; ++pos)
+        ZASR_REQUIRE(img[pos] == 0x5a,
+                     std::string("selftest ") + what + ": the kernel wrote outside its arrays");
+      if (i < segs.size()) pos = segs[i].off + segs[i].bytes;
+    }
+    for (const Seg& g : segs)
+      if (g.dst && g.bytes) std::memcpy(g.dst, img.data() + g.off, g.bytes);
+  }
+};
+
+HotwordDFA search_dfa(const std::string& w, const zasr_st_hotwords& hw, int V) {
+  ZASR_REQUIRE(hw.n >= 0, w + "negative phrase count");
+  std::vector<std::vector<int>> phrases;
+  std::vector<float> scores;
+  const int* tp = hw.tokens;
+  for (int p = 0; p < hw.n; ++p) {
+    ZASR_REQUIRE(hw.tokens && hw.lens && hw.scores, w + "phrases need tokens, lens and scores");
+    ZASR_REQUIRE(hw.lens[p] >= 1, w + "an empty hotword phrase");
+    phrases.emplace_back(tp, tp + hw.lens[p]);
+    for (int tk : phrases.back()) ZASR_REQUIRE(tk >= 0 && tk < V, w + "hotword token id out of range");
+    tp += hw.lens[p];
+    scores.push_back(hw.scores[p]);
+  }
+  return build_hotword_dfa(phrases, scores, V);
+}
+
+struct SearchHw {
+  HotwordDFA dfa;
+  size_t i_cls = 0, i_next = 0, i_delta = 0, i_score = 0;
+  void add(SearchArena& ar) {
+    if (dfa.num_states == 0) return;
+    i_cls = ar.in(dfa.tok2cls.data(), dfa.tok2cls.size());
+    i_next = ar.in(dfa.next.data(), dfa.next.size());
+    i_delta = ar.in(dfa.delta.data(), dfa.delta.size());
+    i_score = ar.in(dfa.node_score.data(), dfa.node_score.size());
+  }
+  HotwordTables tables(const SearchArena& ar) const {
+    HotwordTables t{};
+    if (dfa.num_states == 0) return t;
+    t.num_states = dfa.num_states;
+    t.num_cls = dfa.num_cls;
+    t.tok2cls = ar.at<int>(i_cls);
+    t.next = ar.at<int>(i_next);
+    t.delta = ar.at<double>(i_delta);
+    t.node_score = ar.at<double>(i_score);
+    return t;
+  }
+};
+
+// the state arrays checked against what the kernels index with them, then laid into the arena
+struct SearchSt {
+  size_t i[15];
+  static void check(const std::string& w, const zasr_st_state& st, int V, int max_nh, int room,
+                    int num_states, bool parents) {
+    ZASR_REQUIRE(st.S >= 1 && st.S <= 4096, w + "1 <= S <= 4096");
+    ZASR_REQUIRE(st.Hmax >= 1 && st.Hmax <= 16, w + "1 <= Hmax <= 16");
+    ZASR_REQUIRE(st.node_cap >= 1 && st.node_cap <= (1 << 24), w + "node_cap out of range");
+    ZASR_REQUIRE(st.lp && st.lpf && st.hash && st.len && st.y1 && st.y2 && st.hw && st.node &&
+                     st.nh && st.node_tok && st.node_frame && st.node_parent && st.node_lp &&
+                     st.node_stats && st.node_count,
+                 w + "null state array");
+    for (int s = 0; s < st.S; ++s) {
+      const int nc = st.node_count[s];
+      ZASR_REQUIRE(nc >= 0 && (long)nc + room <= st.node_cap,
+                   w + "node_cap too small for node_count and the nodes one call can add");
+      ZASR_REQUIRE(st.nh[s] >= 0 && st.nh[s] <= max_nh, w + "nh out of range");
+      for (int h = 0; h < st.Hmax; ++h) {
+        const int o = s * st.Hmax + h;
+        const bool live = h < st.nh[s] || h == 0;  // the final pick reads slot 0 of an empty stream
+        if (!live) continue;
+        ZASR_REQUIRE(st.y1[o] >= 0 && st.y1[o] < V && st.y2[o] >= 0 && st.y2[o] < V,
+                     w + "context token out of range");
+        ZASR_REQUIRE(st.hw[o] >= 0 && st.hw[o] < (num_states > 0 ? num_states : 1),
+                     w + "hotword state out of range");
+        ZASR_REQUIRE(st.node[o] >= -1 && st.node[o] < nc, w + "node out of range");
+        ZASR_REQUIRE(st.len[o] >= 0 && st.len[o] < (1 << 30), w + "len out of range");
+      }
+      if (parents)
+        for (int n = 0; n < nc; ++n) {
+          const int pr = st.node_parent[(size_t)s * st.node_cap + n];
+          ZASR_REQUIRE(pr >= -1 && pr < n, w + "node_parent must lie in [-1, own index)");
+        }
+    }
+  }
+  void add(SearchArena& ar, const zasr_st_state& st) {
+    const size_t sl = (size_t)st.S * st.Hmax, nn = (size_t)st.S * st.node_cap;
+    i[0] = ar.io(st.lp, sl);
+    i[1] = ar.io(st.lpf, sl);
+    i[2] = ar.io(st.hash, sl);
+    i[3] = ar.io(st.len, sl);
+    i[4] = ar.io(st.y1, sl);
+    i[5] = ar.io(st.y2, sl);
+    i[6] = ar.io(st.hw, sl);
+    i[7] = ar.io(st.node, sl);
+    i[8] = ar.io(st.nh, (size_t)st.S);
+    i[9] = ar.io(st.node_tok, nn);
+    i[10] = ar.io(st.node_frame, nn);
+    i[11] = ar.io(st.node_parent, nn);
+    i[12] = ar.io(st.node_lp, nn);
+    i[13] = ar.io(st.node_stats, nn * 4);
+    i[14] = ar.io(st.node_count, (size_t)st.S);
+  }
+  SearchState dev(const SearchArena& ar, int node_cap) const {
+    SearchState d{};
+    d.lp = ar.at<double>(i[0]);
+    d.lpf = ar.at<int>(i[1]);
+    d.hash = ar.at<unsigned long long>(i[2]);
+    d.len = ar.at<int>(i[3]);
+    d.y1 = ar.at<int>(i[4]);
+    d.y2 = ar.at<int>(i[5]);
+    d.hw = ar.at<int>(i[6]);
+    d.node = ar.at<int>(i[7]);
+    d.nh = ar.at<int>(i[8]);
+    d.node_tok = ar.at<int>(i[9]);
+    d.node_frame = ar.at<int>(i[10]);
+    d.node_parent = ar.at<int>(i[11]);
+    d.node_lp = ar.at<double>(i[12]);
+    d.node_stats = ar.at<float4>(i[13]);
+    d.node_count = ar.at<int>(i[14]);
+    d.node_cap = node_cap;
+    return d;
+  }
+};
+
+// the full decoder-context table of the last (V, D, a, b), kept on the device between calls (a
+// chain passes the same table every frame)
+struct SearchTableCache {
+  int V = 0, D = 0;
+  std::vector<float> a, b;
+  std::unique_ptr<DevBuf> d;
+  const float* get(int V_, int D_, const float* a_, const float* b_) {
+    const size_t n = (size_t)V_ * D_;
+    if (d && V == V_ && D == D_ && std::memcmp(a.data(), a_, n * 4) == 0 &&
+        std::memcmp(b.data(), b_, n * 4) == 0)
+      return d->as<float>();
+    d.reset();
+    std::vector<float> tab((size_t)V_ * n);
+    for (int y2 = 0; y2 < V_; ++y2)
+      for (int y1 = 0; y1 < V_; ++y1) {
+        float* row = tab.data() + ((size_t)y2 * V_ + y1) * D_;
+        for (int k = 0; k < D_; ++k) row[k] = a_[(size_t)y2 * D_ + k] + b_[(size_t)y1 * D_ + k];
+      }
+    d.reset(new DevBuf(tab.size() * 4));
+    up(*d, tab.data(), tab.size() * 4);
+    V = V_;
+    D = D_;
+    a.assign(a_, a_ + n);
+    b.assign(b_, b_ + n);
+    return d->as<float>();
+  }
+};
+SearchTableCache& search_table_cache() {
+  static SearchTableCache* c = new SearchTableCache;  // outlives the HIP runtime's teardown
+  return *c;
+}
+
+struct SearchTab {
+  size_t i_enc = 0, i_off = 0, i_J = 0;
+  long jrows = 0;
+  static void check(const std::string& w, const zasr_st_table& tb, int V, int S, const int* enc_len,
+                    long rows) {
+    ZASR_REQUIRE(tb.D >= 4 && tb.D % 4 == 0 && tb.D <= 512, w + "joiner dim must be a multiple of 4, <= 512");
+    ZASR_REQUIRE(tb.jfmt >= 0 && tb.jfmt <= 5, w + "J format 0 .. 5");
+    ZASR_REQUIRE(tb.jfmt < 2 || tb.D == 256 || tb.D == 512, w + "fragment-order J: joiner dim 256 or 512");
+    ZASR_REQUIRE((size_t)V * V * tb.D <= ((size_t)1 << 27), w + "decoder table beyond 2^27 floats");
+    ZASR_REQUIRE(tb.a && tb.b && tb.enc && tb.enc_off && tb.J, w + "null table argument");
+    ZASR_REQUIRE(tb.enc_rows >= 1, w + "enc_rows >= 1");
+    for (int s = 0; s < S; ++s)
+      ZASR_REQUIRE(tb.enc_off[s] >= 0 && (long)tb.enc_off[s] + enc_len[s] <= tb.enc_rows,
+                   w + "enc_off + enc_len beyond enc_rows");
+    ZASR_REQUIRE(tb.j_bytes == (long)bytes(tb, rows), w + "j_bytes is not the J format's size");
+  }
+  static int images(int jfmt) { return jfmt == 4 ? 3 : jfmt == 3 || jfmt == 5 ? 2 : 1; }
+  static size_t bytes(const zasr_st_table& tb, long rows) {
+    if (tb.jfmt == 0) return (size_t)rows * tb.D * 4;
+    if (tb.jfmt == 1) return (size_t)rows * tb.D * 2;
+    return (size_t)joiner_packed_rows(rows) * tb.D * 2 * images(tb.jfmt);
+  }
+  void add(SearchArena& ar, const zasr_st_table& tb, int S, long rows) {
+    jrows = joiner_packed_rows(rows);
+    i_enc = ar.in(tb.enc, (size_t)tb.enc_rows * tb.D);
+    i_off = ar.in(tb.enc_off, (size_t)S);
+    i_J = ar.add(tb.J, bytes(tb, rows), tb.J);
+  }
+  DecTable dev(const SearchArena& ar, const zasr_st_table& tb, int V, const int* d_enc_len) const {
+    DecTable dt{search_table_cache().get(V, tb.D, tb.a, tb.b), V, ar.at<float>(i_enc),
+                ar.at<int>(i_off), d_enc_len, ar.at<void>(i_J), tb.D,
+                tb.jfmt == 1 || tb.jfmt == 2 ? 1 : 0};
+    dt.j_packed = tb.jfmt >= 2 ? 1 : 0;
+    dt.j_pieces = tb.jfmt == 3 ? 2 : tb.jfmt == 4 ? 3 : tb.jfmt == 5 ? kPiecesF16 : 0;
+    dt.j_plane = jrows * tb.D;
+    return dt;
+  }
+};
+
+void check_search_common(const std::string& w, int V, int S, const int* enc_len) {
+  ZASR_REQUIRE(V >= 4 && V % 4 == 0 && V <= 4096, w + "vocabulary size must be a multiple of 4, <= 4096");
+  for (int s = 0; s < S; ++s)
+    ZASR_REQUIRE(enc_len[s] >= 0 && enc_len[s] <= (1 << 24), w + "enc_len out of range");
+}
+}  // namespace
+
+void selftest_hotword_dfa(int V, const zasr_st_hotwords& hw, int cap, int* num_states,
+                          int* num_cls, int* tok2cls, int* next, double* delta, double* node_score) {
+  const std::string w = "selftest hotword_dfa: ";
+  ZASR_REQUIRE(V >= 1, w + "V >= 1");
+  const HotwordDFA dfa = search_dfa(w, hw, V);
+  *num_states = dfa.num_states;
+  *num_cls = dfa.num_cls;
+  for (int v = 0; v < V; ++v) tok2cls[v] = dfa.num_states ? dfa.tok2cls[v] : -1;
+  ZASR_REQUIRE((long)dfa.num_states * dfa.num_cls <= cap && dfa.num_states <= cap,
+               w + "cap too small for the automaton");
+  std::copy(dfa.next.begin(), dfa.next.end(), next);
+  std::copy(dfa.delta.begin(), dfa.delta.end(), delta);
+  std::copy(dfa.node_score.begin(), dfa.node_score.end(), node_score);
+}
+
+void selftest_search_step(int V, int beam, int t, const int* enc_len, const zasr_st_state& st,
+                          const float* logits, const zasr_st_hotwords& hw, const zasr_st_table* tab) {
+  const std::string w = "selftest search_step: ";
+  ZASR_REQUIRE(st.S >= 1 && st.S <= 4096, w + "1 <= S <= 4096");
+  check_search_common(w, V, st.S, enc_len);
+  ZASR_REQUIRE(beam >= 1 && beam <= 16 && beam <= st.Hmax, w + "beam out of range");
+  SearchHw h;
+  h.dfa = search_dfa(w, hw, V);
+  const bool init = t < 0;
+  if (init) {
+    ZASR_REQUIRE(st.Hmax >= 1 && st.Hmax <= 16 && st.node_cap >= beam, w + "Hmax / node_cap out of range");
+    ZASR_REQUIRE(st.lp && st.lpf && st.hash && st.len && st.y1 && st.y2 && st.hw && st.node &&
+                     st.nh && st.node_tok && st.node_frame && st.node_parent && st.node_lp &&
+                     st.node_stats && st.node_count,
+                 w + "null state array");
+  } else {
+    SearchSt::check(w, st, V, beam, beam, h.dfa.num_states, false);
+    ZASR_REQUIRE(logits != nullptr, w + "null logits");
+  }
+  const long rows = (long)st.S * st.Hmax;
+  if (tab) SearchTab::check(w, *tab, V, st.S, enc_len, rows);
+  SearchArena ar;
+  SearchSt ss;
+  SearchTab tb;
+  ss.add(ar, st);
+  h.add(ar);
+  const size_t i_len = ar.in(enc_len, (size_t)st.S);
+  const size_t i_lg = init ? 0 : ar.in(logits, (size_t)rows * V);
+  if (tab) tb.add(ar, *tab, st.S, rows);
+  ar.upload();
+  const SearchState ds = ss.dev(ar, st.node_cap);
+  DecTable dt{};
+  if (tab) dt = tb.dev(ar, *tab, V, ar.at<int>(i_len));
+  if (init) {
+    launch_search_init(ds, st.S, st.Hmax, nullptr);
+    if (tab) launch_table_init(dt, st.S, st.Hmax, nullptr);
+  } else {
+    launch_search_step(ds, ar.at<float>(i_lg), V, st.S, st.Hmax, beam, t, ar.at<int>(i_len),
+                       h.tables(ar), tab ? &dt : nullptr, nullptr);
+  }
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  ar.download("search_step");
+}
+
+void selftest_greedy_spec(int V, int F, int init, int parity, const int* enc_len, int* t_cur,
+                          int* active, const zasr_st_state& st, const float* logits,
+                          const zasr_st_hotwords& hw, const zasr_st_table& tab) {
+  const std::string w = "selftest greedy_spec: ";
+  ZASR_REQUIRE(st.S >= 1 && st.S <= 4096, w + "1 <= S <= 4096");
+  check_search_common(w, V, st.S, enc_len);
+  ZASR_REQUIRE(F == 4 || F == 8, w + "window must be 4 or 8 frames");
+  ZASR_REQUIRE(init >= 0 && init <= 2 && (parity == 0 || parity == 1), w + "init 0 .. 2, parity 0 / 1");
+  ZASR_REQUIRE(st.Hmax == 1, w + "beam 1: Hmax = 1");
+  SearchHw h;
+  h.dfa = search_dfa(w, hw, V);
+  if (init == 0) {
+    SearchSt::check(w, st, V, 1, 1, h.dfa.num_states, false);
+    for (int s = 0; s < st.S; ++s) {
+      ZASR_REQUIRE(t_cur[s] >= 0 && t_cur[s] <= (1 << 24), w + "t_cur out of range");
+      ZASR_REQUIRE(st.nh[s] == 1, w + "nh = 1");
+    }
+  } else {
+    ZASR_REQUIRE(st.node_cap >= 1 && st.node_cap <= (1 << 24), w + "node_cap out of range");
+    ZASR_REQUIRE(st.lp && st.lpf && st.hash && st.len && st.y1 && st.y2 && st.hw && st.node &&
+                     st.nh && st.node_tok && st.node_frame && st.node_parent && st.node_lp &&
+                     st.node_stats && st.node_count,
+                 w + "null state array");
+  }
+  ZASR_REQUIRE(init == 2 || logits != nullptr, w + "null logits");
+  const long rows = (long)st.S * F;
+  SearchTab::check(w, tab, V, st.S, enc_len, rows);
+  SearchArena ar;
+  SearchSt ss;
+  SearchTab tb;
+  ss.add(ar, st);
+  h.add(ar);
+  const size_t i_len = ar.in(enc_len, (size_t)st.S);
+  const size_t i_t = ar.io(t_cur, (size_t)st.S);
+  const size_t i_act = ar.io(active, 2);
+  const size_t i_lg = init == 2 ? 0 : ar.in(logits, (size_t)rows * V);
+  tb.add(ar, tab, st.S, rows);
+  ar.upload();
+  const SearchState ds = ss.dev(ar, st.node_cap);
+  const DecTable dt = tb.dev(ar, tab, V, ar.at<int>(i_len));
+  if (init != 0) {
+    launch_search_init(ds, st.S, 1, nullptr);
+    launch_greedy_spec_init(dt, st.S, F, ar.at<int>(i_t), ar.at<int>(i_act), nullptr);
+  }
+  if (init != 2)
+    launch_greedy_spec(ds, ar.at<float>(i_lg), V, st.S, F, ar.at<int>(i_t), ar.at<int>(i_len),
+                       h.tables(ar), dt, ar.at<int>(i_act), parity, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  ar.download("greedy_spec");
+}
+
+void selftest_search_final(int V, const zasr_st_state& st, const zasr_st_hotwords& hw, int out_cap,
+                           int* out_tok, int* out_frame, double* out_lp, float* out_stats,
+                           int* out_count) {
+  const std::string w = "selftest search_final: ";
+  ZASR_REQUIRE(V >= 1 && V <= 4096, w + "V out of range");
+  ZASR_REQUIRE(out_cap >= 1 && out_cap <= (1 << 24), w + "out_cap out of range");
+  SearchHw h;
+  h.dfa = search_dfa(w, hw, V);
+  SearchSt::check(w, st, V, st.Hmax, 0, h.dfa.num_states, true);
+  SearchArena ar;
+  SearchSt ss;
+  ss.add(ar, st);
+  h.add(ar);
+  const size_t n = (size_t)st.S * out_cap;
+  const size_t i_tok = ar.io(out_tok, n), i_fr = ar.io(out_frame, n), i_lp = ar.io(out_lp, n),
+               i_st = ar.io(out_stats, n * 4), i_cnt = ar.io(out_count, (size_t)st.S);
+  ar.upload();
+  launch_search_final(ss.dev(ar, st.node_cap), st.S, st.Hmax, h.tables(ar), out_cap,
+                      ar.at<int>(i_tok), ar.at<int>(i_fr), ar.at<double>(i_lp),
+                      ar.at<float4>(i_st), ar.at<int>(i_cnt), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  ar.download("search_final");
 }
 
 }  // namespace zasr

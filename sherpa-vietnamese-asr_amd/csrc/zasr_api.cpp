@@ -840,6 +840,51 @@ int zasr_selftest_nonlin(int32_t mode, int32_t H, int32_t nseq, const int32_t* L
   });
 }
 
+int zasr_selftest_search_step(int32_t V, int32_t beam, int32_t t, const int32_t* enc_len,
+                              const zasr_st_state* st, const float* logits,
+                              const zasr_st_hotwords* hw, const zasr_st_table* tab) {
+  if (!enc_len || !st || !hw || (t >= 0 && !logits)) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_search_step(V, beam, t, enc_len, *st, logits, *hw, tab);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_greedy_spec(int32_t V, int32_t F, int32_t init, int32_t parity,
+                              const int32_t* enc_len, int32_t* t_cur, int32_t* active,
+                              const zasr_st_state* st, const float* logits,
+                              const zasr_st_hotwords* hw, const zasr_st_table* tab) {
+  if (!enc_len || !t_cur || !active || !st || !hw || !tab)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_greedy_spec(V, F, init, parity, enc_len, t_cur, active, *st, logits, *hw, *tab);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_search_final(int32_t V, const zasr_st_state* st, const zasr_st_hotwords* hw,
+                               int32_t out_cap, int32_t* out_tok, int32_t* out_frame,
+                               double* out_lp, float* out_stats, int32_t* out_count) {
+  if (!st || !hw || !out_tok || !out_frame || !out_lp || !out_stats || !out_count)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_search_final(V, *st, *hw, out_cap, out_tok, out_frame, out_lp, out_stats,
+                                out_count);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_hotword_dfa(int32_t V, const zasr_st_hotwords* hw, int32_t cap,
+                              int32_t* num_states, int32_t* num_cls, int32_t* tok2cls,
+                              int32_t* next, double* delta, double* node_score) {
+  if (!hw || !num_states || !num_cls || !tok2cls || !next || !delta || !node_score)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_hotword_dfa(V, *hw, cap, num_states, num_cls, tok2cls, next, delta, node_score);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const float* W1,
                          const float* b1, const float* W2, const float* b2,
                          const float* byp_orig, const float* byp_scale, float* X) {

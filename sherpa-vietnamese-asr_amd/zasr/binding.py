@@ -43,7 +43,8 @@ EXPORTS = (
     "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm", "zasr_selftest_joiner",
     "zasr_selftest_dwconv1d", "zasr_selftest_conv1", "zasr_selftest_convnext",
     "zasr_selftest_bias_norm", "zasr_selftest_attn_weights", "zasr_selftest_attn_sa",
-    "zasr_selftest_nonlin",
+    "zasr_selftest_nonlin", "zasr_selftest_search_step", "zasr_selftest_greedy_spec",
+    "zasr_selftest_search_final", "zasr_selftest_hotword_dfa",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -78,6 +79,24 @@ class _Config(C.Structure):
         ("device_id", C.c_int32),
         ("precision", C.c_int32),
     ]
+
+
+class _StState(C.Structure):  # include/zasr.h zasr_st_state
+    _fields_ = [("S", C.c_int32), ("Hmax", C.c_int32), ("node_cap", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("lp", "lpf", "hash", "len", "y1", "y2", "hw", "node", "nh",
+                                  "node_tok", "node_frame", "node_parent", "node_lp",
+                                  "node_stats", "node_count")]
+
+
+class _StHotwords(C.Structure):
+    _fields_ = [("tokens", C.c_void_p), ("lens", C.c_void_p), ("scores", C.c_void_p),
+                ("n", C.c_int32)]
+
+
+class _StTable(C.Structure):
+    _fields_ = [("D", C.c_int32), ("jfmt", C.c_int32), ("enc_rows", C.c_int32),
+                ("a", C.c_void_p), ("b", C.c_void_p), ("enc", C.c_void_p),
+                ("enc_off", C.c_void_p), ("J", C.c_void_p), ("j_bytes", C.c_int64)]
 
 
 _lib = None
@@ -282,6 +301,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_nonlin.argtypes = [I32] * 3 + [C.POINTER(I32), I32, I32] + [fp] * 3 + [
         C.POINTER(C.c_uint16), fp]
     lib.zasr_selftest_nonlin.restype = C.c_int
+    sp, hp, tp = C.POINTER(_StState), C.POINTER(_StHotwords), C.POINTER(_StTable)
+    ip32 = C.POINTER(I32)
+    lib.zasr_selftest_search_step.argtypes = [I32, I32, I32, ip32, sp, fp, hp, tp]
+    lib.zasr_selftest_search_step.restype = C.c_int
+    lib.zasr_selftest_greedy_spec.argtypes = [I32] * 4 + [ip32] * 3 + [sp, fp, hp, tp]
+    lib.zasr_selftest_greedy_spec.restype = C.c_int
+    lib.zasr_selftest_search_final.argtypes = [I32, sp, hp, I32, ip32, ip32,
+                                               C.POINTER(C.c_double), fp, ip32]
+    lib.zasr_selftest_search_final.restype = C.c_int
+    lib.zasr_selftest_hotword_dfa.argtypes = [I32, hp, I32, ip32, ip32, ip32, ip32,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.zasr_selftest_hotword_dfa.restype = C.c_int
     # device audio front end (zasr/audio.py)
     lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
     lib.zasr_audio_create.restype = C.c_int
@@ -404,6 +435,149 @@ def selftest_joiner(mode: str, J, W, bias, out, layout: int = 0, live_t=None, li
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return out
+
+
+
+# ---- the transducer search kernels alone (include/zasr.h zasr_selftest_search_*) ----
+SEARCH_STATE_FIELDS = (("lp", np.float64), ("lpf", np.int32), ("hash", np.uint64),
+                       ("len", np.int32), ("y1", np.int32), ("y2", np.int32), ("hw", np.int32),
+                       ("node", np.int32))
+SEARCH_NODE_FIELDS = (("node_tok", np.int32), ("node_frame", np.int32),
+                      ("node_parent", np.int32), ("node_lp", np.float64))
+
+
+def search_state_alloc(S: int, Hmax: int, node_cap: int, fill: int = 0x6b) -> dict:
+    """A search state of S streams x Hmax slots as a dict of numpy arrays, every byte `fill`
+    (what a call does not write stays recognisable): the SEARCH_STATE_FIELDS [S][Hmax], nh [S],
+    the SEARCH_NODE_FIELDS [S][node_cap], node_stats [S][node_cap][4] and node_count [S]."""
+    def arr(shape, dt):
+        a = np.empty(shape, dtype=dt)
+        a.view(np.uint8)[...] = fill
+        return a
+    st = {k: arr((S, Hmax), dt) for k, dt in SEARCH_STATE_FIELDS}
+    st["nh"] = arr((S,), np.int32)
+    st.update({k: arr((S, node_cap), dt) for k, dt in SEARCH_NODE_FIELDS})
+    st["node_stats"] = arr((S, node_cap, 4), np.float32)
+    st["node_count"] = arr((S,), np.int32)
+    return st
+
+
+def _st_struct(st: dict):
+    S, Hmax = st["lp"].shape
+    c = _StState(S, Hmax, st["node_tok"].shape[1])
+    for k, dt in SEARCH_STATE_FIELDS + SEARCH_NODE_FIELDS + (
+            ("nh", np.int32), ("node_stats", np.float32), ("node_count", np.int32)):
+        a = st[k]
+        if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"search state field {k}: a writable C-contiguous {dt.__name__} array")
+        setattr(c, k, a.ctypes.data)
+    return c
+
+
+def _hw_struct(phrases, scores):
+    phrases = [list(p) for p in (phrases or [])]
+    toks = np.ascontiguousarray([t for p in phrases for t in p], dtype=np.int32)
+    lens = np.ascontiguousarray([len(p) for p in phrases], dtype=np.int32)
+    sc = np.ascontiguousarray(list(scores or []), dtype=np.float32)
+    if len(sc) != len(phrases):
+        raise ValueError("one score per hotword phrase")
+    return _StHotwords(toks.ctypes.data, lens.ctypes.data, sc.ctypes.data, len(phrases)), (toks, lens, sc)
+
+
+def _tab_struct(tab: dict):
+    """tab: D, jfmt, a, b [V][D] f32, enc [rows][D] f32, enc_off [S] i32, J (uint8 image, in / out)"""
+    a, b, enc = (_f32(tab[k]) for k in ("a", "b", "enc"))
+    off = np.ascontiguousarray(tab["enc_off"], dtype=np.int32)
+    J = tab["J"]
+    if J.dtype != np.uint8 or not J.flags.c_contiguous or not J.flags.writeable:
+        raise ValueError("J: a writable C-contiguous uint8 image")
+    c = _StTable(int(tab["D"]), int(tab["jfmt"]), enc.shape[0], a.ctypes.data, b.ctypes.data,
+                 enc.ctypes.data, off.ctypes.data, J.ctypes.data, J.size)
+    return c, (a, b, enc, off)
+
+
+def _ip(x):
+    return x.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def selftest_search_step(V: int, beam: int, t: int, enc_len, st: dict, logits=None, phrases=None,
+                         scores=None, tab: Optional[dict] = None,
+                         lib_path: Optional[str] = None) -> None:
+    """One frame of launch_search_step on the state `st` (search_state_alloc's dict, updated in
+    place, as is tab["J"]); t < 0: launch_search_init (+ launch_table_init) instead."""
+    lib = load_library(lib_path)
+    el = np.ascontiguousarray(enc_len, dtype=np.int32)
+    lg = None if logits is None else _f32(logits)
+    hw, keep = _hw_struct(phrases, scores)
+    tb, keep2 = _tab_struct(tab) if tab is not None else (None, None)
+    rc = lib.zasr_selftest_search_step(int(V), int(beam), int(t), _ip(el), C.byref(_st_struct(st)),
+                                       None if lg is None else lg.ctypes.data_as(C_FP),
+                                       C.byref(hw), None if tb is None else C.byref(tb))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+
+
+def selftest_greedy_spec(V: int, F: int, init: int, parity: int, enc_len, t_cur, active, st: dict,
+                         logits, tab: dict, phrases=None, scores=None,
+                         lib_path: Optional[str] = None) -> None:
+    """One super-step of launch_greedy_spec (init 1: after the two init launches; 2: those
+    alone); st, t_cur [S] i32, active [2] i32 and tab["J"] are updated in place."""
+    lib = load_library(lib_path)
+    el = np.ascontiguousarray(enc_len, dtype=np.int32)
+    for x in (t_cur, active):
+        if x.dtype != np.int32 or not x.flags.c_contiguous:
+            raise ValueError("t_cur / active: C-contiguous int32 arrays")
+    lg = None if logits is None else _f32(logits)
+    hw, keep = _hw_struct(phrases, scores)
+    tb, keep2 = _tab_struct(tab)
+    rc = lib.zasr_selftest_greedy_spec(int(V), int(F), int(init), int(parity), _ip(el), _ip(t_cur),
+                                       _ip(active), C.byref(_st_struct(st)),
+                                       None if lg is None else lg.ctypes.data_as(C_FP),
+                                       C.byref(hw), C.byref(tb))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+
+
+def selftest_search_final(V: int, st: dict, out_cap: int, phrases=None, scores=None,
+                          fill: int = 0x6b, lib_path: Optional[str] = None) -> dict:
+    """launch_search_final on the state: returns tok, frame [S][out_cap] i32, lp f64, stats
+    [S][out_cap][4] f32 and count [S] i32, every byte `fill` where the kernel wrote nothing."""
+    lib = load_library(lib_path)
+    S = st["lp"].shape[0]
+    out = {"tok": np.empty((S, out_cap), np.int32), "frame": np.empty((S, out_cap), np.int32),
+           "lp": np.empty((S, out_cap), np.float64), "stats": np.empty((S, out_cap, 4), np.float32),
+           "count": np.empty((S,), np.int32)}
+    for a in out.values():
+        a.view(np.uint8)[...] = fill
+    hw, keep = _hw_struct(phrases, scores)
+    rc = lib.zasr_selftest_search_final(int(V), C.byref(_st_struct(st)), C.byref(hw), int(out_cap),
+                                        _ip(out["tok"]), _ip(out["frame"]),
+                                        out["lp"].ctypes.data_as(C.POINTER(C.c_double)),
+                                        out["stats"].ctypes.data_as(C_FP), _ip(out["count"]))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out
+
+
+def selftest_hotword_dfa(V: int, phrases, scores, lib_path: Optional[str] = None) -> dict:
+    """build_hotword_dfa's tables (host only): tok2cls [V], next / delta [states][cls],
+    node_score [states]."""
+    lib = load_library(lib_path)
+    hw, keep = _hw_struct(phrases, scores)
+    n = sum(len(p) for p in phrases) + 1
+    cap = max(n * n, 1)
+    ns, nc = C.c_int32(0), C.c_int32(0)
+    t2c = np.empty(V, np.int32)
+    nxt = np.empty(cap, np.int32)
+    dl, sc = np.empty(cap, np.float64), np.empty(cap, np.float64)
+    dp = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+    rc = lib.zasr_selftest_hotword_dfa(int(V), C.byref(hw), cap, C.byref(ns), C.byref(nc), _ip(t2c),
+                                       _ip(nxt), dp(dl), dp(sc))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    k = ns.value * nc.value
+    return {"tok2cls": t2c, "next": nxt[:k].reshape(ns.value, nc.value).copy(),
+            "delta": dl[:k].reshape(ns.value, nc.value).copy(), "node_score": sc[:ns.value].copy()}
 
 
 def selftest_ffn_h3(Y, W1, b1, W2, b2, X, byp_orig=None, byp_scale=None,
