@@ -469,6 +469,39 @@ int zasr_selftest_ffn_h3(int32_t R, int32_t D, int32_t F, const float* Y, const 
 int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t epi, int32_t a_bf16,
                        int32_t c_bf16, const float* A, const float* W, const float* bias,
                        const float* aux, const float* byp_orig, const float* byp_scale, float* C);
+/* The general GEMMs behind their other operand loaders (same conventions; no reference
+   counterpart: test infrastructure).  Every output holds its buffer's initial contents on
+   entry; guard bytes lie before and behind it on the device, and a changed guard byte returns
+   ZASR_ERR_RUNTIME.  Every argument is checked before a launch; a refused combination returns
+   ZASR_ERR_RUNTIME with a message and leaves later calls unaffected.
+   conv_gemm: conv.4 (which = 4) or conv.7 (which = 7) of Conv2dSubsampling + SwooshR for a
+   ragged batch exactly as a decode runs it: the implicit-im2col loaders ALOAD_CONV2 /
+   ALOAD_CONV3 over one z-slice per sequence, the slices and the GEMM (gemm_f32 / gemm_bf16 /
+   gemm_x3) chosen by the functions the decode itself calls.  T[nseq] fbank frames per sequence,
+   each >= 9; with l2 = (T - 3) / 2 and L = (T - 7) / 2: conv.4 reads A [sum (T - 2)][80][8],
+   W [32][72], writes C [sum l2][39][32] (3x3, stride (2, 2), no padding); conv.7 reads A
+   [sum l2][39][32], W [128][288], writes C [sum L][19][128] (3x3, stride (1, 2)).  W is in the
+   kernels' k order, k = (kt * 3 + kf) * channels + c, and prepared on the device as the model
+   loader prepares a weight.  mode / (a_bf16, c_bf16): ZASR_PRECISION_FP32 and _BF16X3 /
+   _BF16X6 / _F16X3 take (0, 0); _BF16 takes (1, 1) and (0, 0) for both layers and (0, 1) for
+   conv.7; everything else is refused.
+   gemm_aload: one gemm_f32 problem C[:, c_col : c_col + N] = epi(A' W[N][K]^T + bias) with
+   aload 4 (ALOAD_BNRELU: A'[m][k] = max(A[m * lda + k] a_scale[k] + a_shift[k], 0), A [M][lda],
+   epi 0 or 6) or 5 (ALOAD_IM2COL1D: row m = n * Tout + t, column k = q * C + c reads
+   A[(n * Tin + t * stride + q * dil - pad) * lda + c], zero outside [0, Tin); A [ceil(M / Tout)
+   * Tin][lda]; epi 0, 6 or 4 with aux [M][ldaux]).  epi is a GemmEpi value.  C [M][ldc] is
+   passed and returned whole, so what lies outside the N written columns is visible.  What
+   gemm_f32 refuses (another epilogue, K % C, M % Tout, C % 4, lda % 4, K % 4) returns its
+   message. */
+int zasr_selftest_conv_gemm(int32_t mode, int32_t which, int32_t a_bf16, int32_t c_bf16,
+                            int32_t nseq, const int32_t* T, const float* A, const float* W,
+                            const float* bias, float* C);
+int zasr_selftest_gemm_aload(int32_t aload, int32_t M, int32_t K, int32_t N, int32_t lda,
+                             int32_t ldc, int32_t c_col, int32_t epi, const float* A,
+                             const float* W, const float* bias, const float* a_scale,
+                             const float* a_shift, int32_t Tin, int32_t Tout, int32_t C_in,
+                             int32_t stride, int32_t dil, int32_t pad, const float* aux,
+                             int32_t ldaux, float* C);
 /* The joiner kernels alone on one host problem (same conventions): out[M][V] = J[M][D]
    W[V][D]^T + bias through the launcher a decode uses.  mode: ZASR_PRECISION_FP32, _BF16,
    _BF16X3, _BF16X6 or _F16X3.  layout 0: row-major J (f32; rounded to bf16 on upload in the bf16

@@ -329,60 +329,6 @@ void launch_campp_conv2d(const CamppConv2d& a, int ks, hipStream_t st) {
   else ZASR_LAUNCH((campp_conv2d_kernel<1, 32>), grid, dim3(256), 0, st, a);
 }
 
-// y[r][c] = relu(x[r][c] * s[c] + b[c]), c < C (x row stride ldx, y row stride C)
-__global__ void campp_bnrelu_kernel(const float* __restrict__ x, int ldx, long R, int C,
-                                    const float* __restrict__ s, const float* __restrict__ b,
-                                    float* __restrict__ y) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c4n = C / 4;
-  if (i >= R * c4n) return;
-  const long r = i / c4n;
-  const int c = (int)(i - r * c4n) * 4;
-  const float4 v = *reinterpret_cast<const float4*>(x + r * ldx + c);
-  const float4 sv = *reinterpret_cast<const float4*>(s + c), bv = *reinterpret_cast<const float4*>(b + c);
-  *reinterpret_cast<float4*>(y + r * C + c) =
-      make_float4(fmaxf(fmaf(v.x, sv.x, bv.x), 0.f), fmaxf(fmaf(v.y, sv.y, bv.y), 0.f),
-                  fmaxf(fmaf(v.z, sv.z, bv.z), 0.f), fmaxf(fmaf(v.w, sv.w, bv.w), 0.f));
-}
-
-void launch_campp_bnrelu(const float* x, int ldx, long R, int C, const float* s, const float* b,
-                         float* y, hipStream_t st) {
-  ZASR_REQUIRE(C % 4 == 0 && ldx % 4 == 0, "campp bnrelu: channels must be multiples of 4");
-  const long n = R * (C / 4);
-  if (n <= 0) return;
-  ZASR_LAUNCH(campp_bnrelu_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, st, x, ldx,
-                     R, C, s, b, y);
-}
-
-// im2col of a 1-D convolution over sequences of Tin frames (channels-last, row stride ldx):
-// out[n * Tout + t][k * C + c] = x[n * Tin + t * stride + k * dil - pad][c] (0 outside)
-__global__ void campp_im2col1d_kernel(const float* __restrict__ x, int ldx, int N, int Tin,
-                                      int Tout, int C, int K, int stride, int dil, int pad,
-                                      float* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c4n = C / 4;
-  const long total = (long)N * Tout * K * c4n;
-  if (i >= total) return;
-  const int c = (int)(i % c4n) * 4;
-  const long j = i / c4n;
-  const int k = (int)(j % K);
-  const long r = j / K;
-  const int n = (int)(r / Tout), t = (int)(r - (long)n * Tout);
-  const int ts = t * stride + k * dil - pad;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ts >= 0 && ts < Tin) v = *reinterpret_cast<const float4*>(x + ((long)n * Tin + ts) * ldx + c);
-  *reinterpret_cast<float4*>(out + r * ((long)K * C) + k * C + c) = v;
-}
-
-void launch_campp_im2col1d(const float* x, int ldx, int N, int Tin, int Tout, int C, int K,
-                           int stride, int dil, int pad, float* out, hipStream_t st) {
-  ZASR_REQUIRE(C % 4 == 0 && ldx % 4 == 0, "campp im2col: channels must be multiples of 4");
-  const long n = (long)N * Tout * K * (C / 4);
-  if (n <= 0) return;
-  ZASR_LAUNCH(campp_im2col1d_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, st, x,
-                     ldx, N, Tin, Tout, C, K, stride, dil, pad, out);
-}
-
 // CAM context mask (CAMLayer.forward: context = mean_t(x) + seg_pooling(x); m = sigmoid(
 // linear2(relu(linear1(context))))), block per (sequence n, segment g): 128 input channels
 // (one per thread), the per-segment mask expanded to every frame of the segment:

@@ -72,6 +72,28 @@ struct DLin {
   const float* hb = nullptr;
 };
 
+// Conv2dSubsampling's conv.4 / conv.7: the general GEMMs behind the implicit-im2col loaders
+// ALOAD_CONV2 / ALOAD_CONV3, one z-slice per sequence (engine_encoder.cpp; the decode and
+// zasr_selftest_conv_gemm share both functions, so the self-test makes the decode's launch).
+// Route: bf16 weights when the activations on either side are bf16 or the weight has no split
+// image, else the split pieces, else f32.
+enum ConvGemmRoute { CONV_GEMM_F32, CONV_GEMM_BF16, CONV_GEMM_X3 };
+ConvGemmRoute frontend_conv_route(const DLin& l, bool a_bf16, bool c_bf16);
+// fills B / bias / N / ldc of p from l and launches EPI_SWOOSHR on the route; p carries A, C,
+// the slices, num_slices and max_M
+void launch_frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_bf16, bool c_bf16,
+                               int pieces, hipStream_t st);
+// The z-slices of both layers from the fbank frames per sequence T (each >= 9): conv.0 leaves
+// T - 2 rows of [80][8], conv.4 l2 = (T - 3) / 2 rows of [39][32], conv.7 L = (T - 7) / 2 rows
+// of [19][128], packed sequence after sequence; a slice's M is its output positions (rows x
+// frequencies), K the 9 taps x input channels.
+struct FrontendConvSlices {
+  std::vector<GemmSlice> c2, c3;  // conv.4, conv.7
+  int max_M2 = 0, max_M3 = 0;
+  long rows_c1 = 0, rows_c2 = 0, rows_L = 0;  // sum of T - 2, l2, L
+};
+FrontendConvSlices frontend_conv_slices(const int* T, int nseq);
+
 struct DLayer {
   DLin attn_in, sa_in[2], sa_out[2], ff_in[3], ff_out[3], na_in, na_out, cv_in[2], cv_out[2];
   float* cv_dw_w[2] = {nullptr, nullptr};

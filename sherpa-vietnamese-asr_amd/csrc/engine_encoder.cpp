@@ -328,24 +328,47 @@ float* Engine::layer_forward(const StackCtx& c, const DLayer& Ly, float* X, floa
   return X;
 }
 
-// bf16 weights when the activations on either side are bf16 or the weight has them, else the
-// split pieces, else f32
-void Engine::frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_bf16, bool c_bf16) {
+ConvGemmRoute frontend_conv_route(const DLin& l, bool a_bf16, bool c_bf16) {
+  if (l.wh && (a_bf16 || c_bf16)) return CONV_GEMM_BF16;
+  if (l.wx) return CONV_GEMM_X3;
+  return l.wh ? CONV_GEMM_BF16 : CONV_GEMM_F32;
+}
+
+void launch_frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_bf16, bool c_bf16,
+                               int pieces, hipStream_t st) {
   p.B = l.w;
   p.sbk = 1;
   p.sbn = l.K;
   p.ldc = l.N;
   p.bias = l.b;
   p.N = l.N;
+  switch (frontend_conv_route(l, a_bf16, c_bf16)) {
+    case CONV_GEMM_BF16: return gemm_bf16(p, l.wh, EPI_SWOOSHR, aload, st, a_bf16, c_bf16);
+    case CONV_GEMM_X3: return gemm_x3(p, l.wx, (long)l.N * l.K, EPI_SWOOSHR, aload, st, pieces);
+    case CONV_GEMM_F32: return gemm_f32(p, EPI_SWOOSHR, aload, false, st);
+  }
+}
+
+FrontendConvSlices frontend_conv_slices(const int* T, int nseq) {
+  FrontendConvSlices y;
+  y.c2.resize(nseq);
+  y.c3.resize(nseq);
+  for (int b = 0; b < nseq; ++b) {
+    const int t1 = T[b] - 2, l2 = (T[b] - 3) / 2, L = (T[b] - 7) / 2;
+    y.c2[b] = GemmSlice{y.rows_c1 * 640, 0, y.rows_c2 * 39 * 32, 0, l2 * 39, 72, 0, 0};
+    y.c3[b] = GemmSlice{y.rows_c2 * 39 * 32, 0, y.rows_L * 19 * 128, 0, L * 19, 288, 0, 0};
+    y.max_M2 = std::max(y.max_M2, l2 * 39);
+    y.max_M3 = std::max(y.max_M3, L * 19);
+    y.rows_c1 += t1;
+    y.rows_c2 += l2;
+    y.rows_L += L;
+  }
+  return y;
+}
+
+void Engine::frontend_conv_gemm(GemmParams& p, const DLin& l, int aload, bool a_bf16, bool c_bf16) {
   prof_begin("frontend_conv");
-  if (l.wh && (a_bf16 || c_bf16))
-    gemm_bf16(p, l.wh, EPI_SWOOSHR, aload, st_, a_bf16, c_bf16);
-  else if (l.wx)
-    gemm_x3(p, l.wx, (long)l.N * l.K, EPI_SWOOSHR, aload, st_, prec_.pieces);
-  else if (l.wh)
-    gemm_bf16(p, l.wh, EPI_SWOOSHR, aload, st_);
-  else
-    gemm_f32(p, EPI_SWOOSHR, aload, false, st_);
+  launch_frontend_conv_gemm(p, l, aload, a_bf16, c_bf16, prec_.pieces, st_);
   prof_end();
 }
 
@@ -405,11 +428,8 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
   }
   ensure_pos_tables(maxL_all + 192);  // the bf16 attention stages rows up to L + 160
   // frontend conv slices
-  std::vector<GemmSlice> sl_c2(B), sl_c3(B);
-  for (int b = 0; b < B; ++b) {
-    sl_c2[b] = GemmSlice{(long)mc1.off[b] * 640, 0, (long)mc2.off[b] * 39 * 32, 0, l2[b] * 39, 72, 0, 0};
-    sl_c3[b] = GemmSlice{(long)mc2.off[b] * 39 * 32, 0, (long)mL.off[b] * 19 * 128, 0, L[b] * 19, 288, 0, 0};
-  }
+  const FrontendConvSlices fcs = frontend_conv_slices(T.data(), B);
+  const std::vector<GemmSlice>&sl_c2 = fcs.c2, &sl_c3 = fcs.c3;
   // one metadata upload
   MetaPack mp;
   size_t o_fb = mp.add(mfb.off.data(), (B + 1) * 4), o_c1 = mp.add(mc1.off.data(), (B + 1) * 4),
@@ -472,7 +492,7 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
     p.C = reinterpret_cast<float*>(c2);
     p.slices = reinterpret_cast<const GemmSlice*>(d_meta + o_c2s);
     p.num_slices = B;
-    p.max_M = mc2.maxlen * 39;
+    p.max_M = fcs.max_M2;
     frontend_conv_gemm(p, model_.conv4, ALOAD_CONV2, fe16, fe16);
   }
   const int d0 = cfg.dims[0];
@@ -482,7 +502,7 @@ void Engine::run_encoder(const float* d_feats, const std::vector<int>& T, float*
     p.A = reinterpret_cast<const float*>(c2);
     p.slices = reinterpret_cast<const GemmSlice*>(d_meta + o_c3s);
     p.num_slices = B;
-    p.max_M = mL.maxlen * 19;
+    p.max_M = fcs.max_M3;
     if (model_.pw1.wh) {
       // bf16 mode: conv.7 output, the ConvNeXt block and its output stay bf16
       __bf16* x3 = ws<__bf16>("fe_x3_h", (size_t)mL.total * 19 * 128);

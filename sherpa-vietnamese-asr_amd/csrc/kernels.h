@@ -46,6 +46,17 @@ void selftest_gemm_h3r(int M, int K, int N, int epi, const float* A, const float
 void selftest_gemm(int mode, int M, int K, int N, int epi, bool a_bf16, bool c_bf16,
                    const float* A, const float* W, const float* bias, const float* aux,
                    const float* byp_orig, const float* byp_scale, float* C);
+// conv.4 / conv.7 of Conv2dSubsampling for a ragged batch (T[nseq] fbank frames, each >= 9)
+// through the decode's own slice construction and route choice (engine.h frontend_conv_slices /
+// launch_frontend_conv_gemm); W [N][K] in the kernels' k order; C in / out as f32
+void selftest_conv_gemm(int mode, int which, bool a_bf16, bool c_bf16, int nseq, const int* T,
+                        const float* A, const float* W, const float* bias, float* C);
+// one gemm_f32 problem behind ALOAD_BNRELU (4) or ALOAD_IM2COL1D (5): A [rows][lda], the GEMM
+// writes columns [c_col, c_col + N) of C [M][ldc] (in / out: the whole image)
+void selftest_gemm_aload(int aload, int M, int K, int N, int lda, int ldc, int c_col, int epi,
+                         const float* A, const float* W, const float* bias, const float* a_scale,
+                         const float* a_shift, int Tin, int Tout, int Cin, int stride, int dil,
+                         int pad, const float* aux, int ldaux, float* C);
 // out[M][V] = J W^T + bias through the decode's joiner launcher (layout 0: row-major J; 1: J
 // packed on the host in fragment order, W by gemm_rp_pack_weights); out in / out
 void selftest_joiner(int mode, int layout, int M, int V, int D, const float* J, const float* W,
@@ -75,10 +86,6 @@ struct CamppConv2d {
 };
 void campp_conv2d_permute_weights(const float* w, int ks, float* out);
 void launch_campp_conv2d(const CamppConv2d& a, int ks, hipStream_t st);
-void launch_campp_bnrelu(const float* x, int ldx, long R, int C, const float* s, const float* b,
-                         float* y, hipStream_t st);
-void launch_campp_im2col1d(const float* x, int ldx, int N, int Tin, int Tout, int C, int K,
-                           int stride, int dil, int pad, float* out, hipStream_t st);
 struct CamppCamMask {
   const float* h;      // [n * T][128] CAM input (nonlinear2 output)
   const float* w1;     // [64][128] linear1

@@ -6,7 +6,9 @@
 // replaces, and the convolution path's hand-written kernels (ConvolutionModule depthwise conv,
 // conv.0, the ConvNeXt block) and BiasNorm on ragged batches given as per-sequence lengths, and
 // the joiner kernels on row-major and on host-packed J, and the transducer search kernels (one
-// frame, one greedy window, the final pick) on a caller-supplied search state.
+// frame, one greedy window, the final pick) on a caller-supplied search state, and the general
+// GEMMs behind their implicit-im2col and BN-ReLU operand loaders (conv.4 / conv.7 over one
+// z-slice per sequence as a decode launches them; the CAM++ projections of gemm_f32).
 // Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
 #include <algorithm>
 #include <cstring>
@@ -1199,6 +1201,151 @@ void selftest_search_final(int V, const zasr_st_state& st, const zasr_st_hotword
                       ar.at<float4>(i_st), ar.at<int>(i_cnt), nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   ar.download("search_final");
+}
+
+// ---- the GEMMs' implicit-im2col loaders and ragged z-slices ----
+namespace {
+// an output image of n elements (f32, or bf16 as OutBuf) that starts as the caller's, with
+// `guard` elements of 0x5a before it and behind it (guard * element size a multiple of 16)
+struct FramedOut {
+  size_t n, guard, eb;
+  DevBuf d;
+  FramedOut(const float* init, size_t n_, size_t guard_, bool h16)
+      : n(n_), guard(guard_), eb(h16 ? 2 : 4), d((n_ + 2 * guard_) * (h16 ? 2 : 4)) {
+    ZASR_HIP_CHECK(hipMemset(d.p, 0x5a, (n + 2 * guard) * eb));
+    if (n == 0) return;
+    if (h16) ZASR_HIP_CHECK(hipMemcpy(image(), round16(init, n).data(), n * 2, hipMemcpyHostToDevice));
+    else ZASR_HIP_CHECK(hipMemcpy(image(), init, n * 4, hipMemcpyHostToDevice));
+  }
+  unsigned char* image() const { return d.as<unsigned char>() + guard * eb; }
+  void down(float* out, const char* what) const {
+    std::vector<unsigned char> all((n + 2 * guard) * eb);
+    ZASR_HIP_CHECK(hipMemcpy(all.data(), d.p, all.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < guard * eb; ++i) {
+      ZASR_REQUIRE(all[i] == 0x5a, std::string("selftest ") + what + ": the kernel wrote before the first row");
+      ZASR_REQUIRE(all[(guard + n) * eb + i] == 0x5a,
+                   std::string("selftest ") + what + ": the kernel wrote past the last row");
+    }
+    if (n == 0) return;
+    if (eb == 2) {
+      const __bf16* h = reinterpret_cast<const __bf16*>(all.data() + guard * eb);
+      for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
+    } else {
+      std::memcpy(out, all.data() + guard * eb, n * 4);
+    }
+  }
+};
+}  // namespace
+
+void selftest_conv_gemm(int mode, int which, bool a_bf16, bool c_bf16, int nseq, const int* T,
+                        const float* A, const float* W, const float* bias, float* C) {
+  const bool f32 = mode == ZASR_PRECISION_FP32, h16 = mode == ZASR_PRECISION_BF16;
+  const int pieces = mode == ZASR_PRECISION_BF16X3   ? 2
+                     : mode == ZASR_PRECISION_BF16X6 ? 3
+                     : mode == ZASR_PRECISION_F16X3  ? kPiecesF16
+                                                     : 0;
+  ZASR_REQUIRE(f32 || h16 || pieces != 0,
+               "selftest conv_gemm: mode must be ZASR_PRECISION_FP32, _BF16, _BF16X3, _BF16X6 or _F16X3");
+  ZASR_REQUIRE(which == 4 || which == 7, "selftest conv_gemm: which must be 4 (conv.4) or 7 (conv.7)");
+  ZASR_REQUIRE(h16 || (!a_bf16 && !c_bf16), "selftest conv_gemm: bf16 A / C in the bf16 mode only");
+  ZASR_REQUIRE(!a_bf16 || c_bf16, "selftest conv_gemm: bf16 A takes bf16 C");
+  ZASR_REQUIRE(a_bf16 == c_bf16 || which == 7, "selftest conv_gemm: f32 A with bf16 C is conv.7's only");
+  ZASR_REQUIRE(nseq >= 1 && nseq <= 65535, "selftest conv_gemm: 1 .. 65535 sequences");
+  for (int b = 0; b < nseq; ++b)
+    ZASR_REQUIRE(T[b] >= 9 && T[b] <= (1 << 20), "selftest conv_gemm: every T in [9, 2^20]");
+  const FrontendConvSlices fcs = frontend_conv_slices(T, nseq);
+  const bool c4 = which == 4;
+  const int N = c4 ? 32 : 128, K = c4 ? 72 : 288;
+  const size_t na = c4 ? (size_t)fcs.rows_c1 * 640 : (size_t)fcs.rows_c2 * 39 * 32;
+  const size_t nc = c4 ? (size_t)fcs.rows_c2 * 39 * 32 : (size_t)fcs.rows_L * 19 * 128;
+  ZASR_REQUIRE(na < ((size_t)1 << 31) && nc < ((size_t)1 << 31), "selftest conv_gemm: batch too large");
+  const size_t nw = (size_t)N * K;
+  DevBuf dA(na * (a_bf16 ? 2 : 4)), dW(nw * 4), dWx(nw * 2 * (pieces ? stored_pieces(pieces) : 1)),
+      dB((size_t)N * 4), dS((size_t)nseq * sizeof(GemmSlice));
+  up16(dA, A, na, a_bf16);
+  up(dW, W, nw * 4);
+  up(dB, bias, (size_t)N * 4);
+  // the weight's images as the loader prepares them (engine_load.cpp)
+  DLin l;
+  l.w = dW.as<float>();
+  l.b = dB.as<float>();
+  l.N = N;
+  l.K = K;
+  if (h16) {
+    convert_to_bf16(dW.as<float>(), dWx.p, (long)nw, nullptr);
+    l.wh = dWx.p;
+  }
+  if (pieces) {
+    split_to_bf16(dW.as<float>(), dWx.p, (long)nw, pieces, nullptr);
+    l.wx = dWx.p;
+  }
+  const std::vector<GemmSlice>& sl = c4 ? fcs.c2 : fcs.c3;
+  up(dS, sl.data(), (size_t)nseq * sizeof(GemmSlice));
+  FramedOut o(C, nc, (size_t)(c4 ? 39 * 32 : 19 * 128), c_bf16);  // one frame either side
+  GemmParams p{};
+  p.A = dA.as<float>();
+  p.C = reinterpret_cast<float*>(o.image());
+  p.slices = dS.as<GemmSlice>();
+  p.num_slices = nseq;
+  p.max_M = c4 ? fcs.max_M2 : fcs.max_M3;
+  launch_frontend_conv_gemm(p, l, c4 ? ALOAD_CONV2 : ALOAD_CONV3, a_bf16, c_bf16, pieces, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(C, "conv_gemm");
+}
+
+void selftest_gemm_aload(int aload, int M, int K, int N, int lda, int ldc, int c_col, int epi,
+                         const float* A, const float* W, const float* bias, const float* a_scale,
+                         const float* a_shift, int Tin, int Tout, int Cin, int stride, int dil,
+                         int pad, const float* aux, int ldaux, float* C) {
+  const GemmIm2col1d g{Tin, Tout, Cin, stride, dil, pad};
+  const bool bn = aload == ALOAD_BNRELU;
+  ZASR_REQUIRE(bn || aload == ALOAD_IM2COL1D,
+               "selftest gemm_aload: aload must be ALOAD_BNRELU (4) or ALOAD_IM2COL1D (5)");
+  ZASR_REQUIRE(M >= 1 && K >= 1 && N >= 1 && M <= (1 << 20) && K <= (1 << 16) && N <= (1 << 16),
+               "selftest gemm_aload: M, K, N out of range");
+  ZASR_REQUIRE(c_col >= 0 && ldc >= c_col + N && ldc <= (1 << 16),
+               "selftest gemm_aload: columns [c_col, c_col + N) must lie inside ldc");
+  ZASR_REQUIRE(!bn || (a_scale && a_shift), "selftest gemm_aload: ALOAD_BNRELU needs a_scale / a_shift");
+  ZASR_REQUIRE(epi != EPI_MULAUX || (aux != nullptr && ldaux >= N && ldaux <= (1 << 16)),
+               "selftest gemm_aload: EPI_MULAUX needs aux with ldaux >= N");
+  long a_rows = M;
+  if (bn) {
+    ZASR_REQUIRE(lda >= K && lda <= (1 << 16), "selftest gemm_aload: lda >= K");
+  } else {
+    ZASR_REQUIRE(g.Tin >= 1 && g.Tout >= 1 && g.C >= 1 && g.stride >= 1 && g.dil >= 1 && g.pad >= 0 &&
+                     g.Tin <= (1 << 20) && g.stride <= 64 && g.dil <= 64 && g.pad <= 4096,
+                 "selftest gemm_aload: im2col fields out of range");
+    ZASR_REQUIRE(lda >= g.C && lda <= (1 << 16), "selftest gemm_aload: lda >= C");
+    a_rows = (long)cdiv(M, g.Tout) * g.Tin;
+  }
+  const size_t na = (size_t)a_rows * lda, nw = (size_t)N * K, nc = (size_t)M * ldc;
+  ZASR_REQUIRE(na < ((size_t)1 << 31) && nc < ((size_t)1 << 31), "selftest gemm_aload: problem too large");
+  const size_t nx = epi == EPI_MULAUX ? (size_t)M * ldaux : 0;
+  DevBuf dA(na * 4), dW(nw * 4), dB((size_t)N * 4), dSc((size_t)K * 4), dSh((size_t)K * 4), dX(nx * 4);
+  up(dA, A, na * 4);
+  up(dW, W, nw * 4);
+  if (bias) up(dB, bias, (size_t)N * 4);
+  if (bn) {
+    up(dSc, a_scale, (size_t)K * 4);
+    up(dSh, a_shift, (size_t)K * 4);
+  }
+  if (nx) up(dX, aux, nx * 4);
+  FramedOut o(C, nc, (size_t)((ldc + 3) & ~3), false);
+  GemmParams p = dense_gemm_params(dW.as<float>(), bias ? dB.as<float>() : nullptr, N, K, dA.p, lda, M,
+                                   reinterpret_cast<float*>(o.image()) + c_col, ldc);
+  if (nx) {
+    p.aux = dX.as<float>();
+    p.ldaux = ldaux;
+  }
+  if (bn) {
+    p.a_scale = dSc.as<float>();
+    p.a_shift = dSh.as<float>();
+  } else {
+    p.i2c = g;
+  }
+  gemm_f32(p, epi, aload, false, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(C, "gemm_aload");
 }
 
 }  // namespace zasr

@@ -790,6 +790,30 @@ int zasr_selftest_gemm(int32_t mode, int32_t M, int32_t K, int32_t N, int32_t ep
   });
 }
 
+int zasr_selftest_conv_gemm(int32_t mode, int32_t which, int32_t a_bf16, int32_t c_bf16,
+                            int32_t nseq, const int32_t* T, const float* A, const float* W,
+                            const float* bias, float* C) {
+  if (!T || !A || !W || !bias || !C) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_conv_gemm(mode, which, a_bf16 != 0, c_bf16 != 0, nseq, T, A, W, bias, C);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_gemm_aload(int32_t aload, int32_t M, int32_t K, int32_t N, int32_t lda,
+                             int32_t ldc, int32_t c_col, int32_t epi, const float* A,
+                             const float* W, const float* bias, const float* a_scale,
+                             const float* a_shift, int32_t Tin, int32_t Tout, int32_t C_in,
+                             int32_t stride, int32_t dil, int32_t pad, const float* aux,
+                             int32_t ldaux, float* C) {
+  if (!A || !W || !C) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_gemm_aload(aload, M, K, N, lda, ldc, c_col, epi, A, W, bias, a_scale, a_shift,
+                              Tin, Tout, C_in, stride, dil, pad, aux, ldaux, C);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int32_t D,
                          const float* J, const float* W, const float* bias,
                          const int32_t* live_t, const int32_t* live_len, int32_t live_f,

@@ -41,6 +41,7 @@ EXPORTS = (
     "zasr_selftest_gemm_h3r", "zasr_selftest_ffn_h3", "zasr_selftest_ffn_bf16",
     "zasr_selftest_attn_block_map", "zasr_selftest_seam", "zasr_selftest_ffn_bf16_oop",
     "zasr_selftest_ffn_h3_oop", "zasr_selftest_gemm", "zasr_selftest_joiner",
+    "zasr_selftest_conv_gemm", "zasr_selftest_gemm_aload",
     "zasr_selftest_dwconv1d", "zasr_selftest_conv1", "zasr_selftest_convnext",
     "zasr_selftest_bias_norm", "zasr_selftest_attn_weights", "zasr_selftest_attn_sa",
     "zasr_selftest_nonlin", "zasr_selftest_search_step", "zasr_selftest_greedy_spec",
@@ -271,6 +272,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_gemm_h3r.restype = C.c_int
     lib.zasr_selftest_gemm.argtypes = [I32] * 7 + [fp] * 7
     lib.zasr_selftest_gemm.restype = C.c_int
+    lib.zasr_selftest_conv_gemm.argtypes = [I32] * 5 + [C.POINTER(I32)] + [fp] * 4
+    lib.zasr_selftest_conv_gemm.restype = C.c_int
+    lib.zasr_selftest_gemm_aload.argtypes = [I32] * 8 + [fp] * 5 + [I32] * 6 + [fp, I32, fp]
+    lib.zasr_selftest_gemm_aload.restype = C.c_int
     lib.zasr_selftest_joiner.argtypes = [I32] * 5 + [fp] * 3 + [C.POINTER(I32)] * 2 + [I32, fp]
     lib.zasr_selftest_joiner.restype = C.c_int
     lib.zasr_selftest_ffn_h3.argtypes = [I32, I32, I32, fp, fp, fp, fp, fp, fp, fp, fp]
@@ -418,6 +423,63 @@ def selftest_gemm(mode: str, A, W, bias, C, epi: int = 0, a_bf16: bool = False,
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return C
+
+
+def conv_gemm_shapes(which: int, T):
+    """(A shape, W shape, C shape) of zasr_selftest_conv_gemm for conv.4 / conv.7 on fbank
+    lengths T."""
+    T = _lens(T)
+    t1, l2, L = int((T - 2).sum()), int(((T - 3) // 2).sum()), int(((T - 7) // 2).sum())
+    if which == 4:
+        return (t1, 80, 8), (32, 72), (l2, 39, 32)
+    return (l2, 39, 32), (128, 288), (L, 19, 128)
+
+
+def selftest_conv_gemm(mode: str, which: int, T, A, W, bias, a_bf16: bool = False,
+                       c_bf16: bool = False, fill: float = -777.25,
+                       lib_path: Optional[str] = None) -> np.ndarray:
+    """conv.4 / conv.7 + SwooshR for a ragged batch as a decode launches them
+    (zasr_selftest_conv_gemm; mode: a PRECISIONS name; T: fbank frames per sequence): A, W
+    (k = (kt * 3 + kf) * channels + c), bias as conv_gemm_shapes gives them; returns C, which
+    started as `fill`, as float32."""
+    lib = load_library(lib_path)
+    T, A, W, bias = _lens(T), _f32(A), _f32(W), _f32(bias)
+    out = None
+    if which in (4, 7) and len(T) and int(T.min()) >= 9:
+        sa, sw, sc = conv_gemm_shapes(which, T)
+        assert A.shape == sa and W.shape == sw and bias.shape == (sw[0],)
+        out = np.full(sc, fill, dtype=np.float32)
+    else:  # a refusal under test: the library answers before it reads an operand
+        out = np.full((1,), fill, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C_FP)
+    rc = lib.zasr_selftest_conv_gemm(PRECISIONS[mode], int(which), int(a_bf16), int(c_bf16), len(T),
+                                     T.ctypes.data_as(C.POINTER(C.c_int32)), p(A), p(W), p(bias),
+                                     p(out))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return out
+
+
+def selftest_gemm_aload(aload: int, A, W, bias, C, M: int, lda: int, epi: int = 0, c_col: int = 0,
+                        a_scale=None, a_shift=None, i2c=(0, 0, 0, 1, 1, 0), aux=None,
+                        lib_path: Optional[str] = None) -> np.ndarray:
+    """One gemm_f32 problem behind ALOAD_BNRELU (aload 4) or ALOAD_IM2COL1D (5)
+    (zasr_selftest_gemm_aload): A [rows][lda], W [N][K], C [M][ldc] whole, the GEMM writing its
+    columns [c_col, c_col + N); i2c = (Tin, Tout, C, stride, dil, pad); aux [M][ldaux] for the
+    multiply epilogue.  Returns C's image afterwards."""
+    lib = load_library(lib_path)
+    A, W, C_ = _f32(A), _f32(W), _f32(C).copy()
+    opt = [None if x is None else _f32(x) for x in (bias, a_scale, a_shift, aux)]
+    assert A.ndim == 2 and A.shape[1] == lda and C_.shape[0] == M
+    p = lambda x: None if x is None else x.ctypes.data_as(C_FP)
+    ldaux = 0 if opt[3] is None else opt[3].shape[1]
+    rc = lib.zasr_selftest_gemm_aload(int(aload), int(M), W.shape[1], W.shape[0], int(lda),
+                                      C_.shape[1], int(c_col), int(epi), p(A), p(W), p(opt[0]),
+                                      p(opt[1]), p(opt[2]), *(int(v) for v in i2c), p(opt[3]),
+                                      ldaux, p(C_))
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+    return C_
 
 
 def selftest_joiner(mode: str, J, W, bias, out, layout: int = 0, live_t=None, live_len=None,
