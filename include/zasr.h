@@ -362,6 +362,46 @@ int zasr_seg_trim(zasr_seg* h);
 int zasr_seg_set_profile(zasr_seg* h, int32_t on);
 int zasr_seg_stage_ms(zasr_seg* h, float* ms5);
 
+/* ---- Conv-TasNet overlap separation ----
+   Replaces the reference's separation session (core/overlap_separator.py:45-60, an
+   onnxruntime CPU session over ConvTasNet_Libri2Mix_sepclean_16k) and its per-region call
+   (:281-296).  model_dir holds config.json + model.safetensors (asteroid ConvTasNet state-dict
+   names); reading the reference's .onnx is not supported.  Bad arguments (null pointers,
+   n <= 0, a region shorter than kernel_size = 32 samples or outside the signal) return
+   ZASR_ERR_INVALID, missing model files ZASR_ERR_NOT_FOUND.  A region's result does not depend
+   on the other regions of the call, on its place among them or on the workspace budget. */
+typedef struct zasr_sep zasr_sep;
+int zasr_sep_create(const char* model_dir, int32_t device_id, zasr_sep** out);
+void zasr_sep_destroy(zasr_sep* h);
+/* fewest samples of a region (the encoder's kernel_size) */
+int32_t zasr_sep_min_samples(const zasr_sep* h);
+/* session.run(None, {"mixture": x})[0] (core/overlap_separator.py:291) for n mixtures in one
+   call: region r is samples[offsets[r], offsets[r] + lengths[r]) of the `total` host samples;
+   out (host) holds [2][lengths[r]] per region, regions in order (2 * sum lengths floats): the
+   raw network output, zero from the last whole frame's end to lengths[r]. */
+int zasr_sep_separate(zasr_sep* h, const float* samples, int64_t total, const int64_t* offsets,
+                      const int64_t* lengths, int32_t n, float* out);
+/* the same for regions [starts[r], starts[r] + lengths[r]) of the 16 kHz signal
+   d_audio[0, total) already in HBM (core/overlap_separator.py:283 slices the host array); out
+   is device memory when out_on_device, else host.  Ordered after `stream` (a hipStream_t,
+   0 = none); synchronises before it returns.  Bit-identical to zasr_sep_separate. */
+int zasr_sep_separate_device(zasr_sep* h, const float* d_audio, int64_t total,
+                             const int64_t* starts, const int64_t* lengths, int32_t n, float* out,
+                             int32_t out_on_device, void* stream);
+/* The regions of a call run in launch groups whose activations (7.4 KB per frame of 16 samples)
+   stay within `bytes` (default 4 GiB; a longer region runs alone); zasr_sep_last_groups is the
+   number of groups of the last call.  Not counted in the budget: the call's device copy of the
+   host samples (zasr_sep_separate: 4 bytes per sample) and its output buffer when the output
+   goes to the host (8 bytes per region sample), both allocated for the whole call.  zasr_sep_trim frees the workspace the handle keeps
+   between calls. */
+int zasr_sep_set_budget(zasr_sep* h, int64_t bytes);
+int32_t zasr_sep_last_groups(const zasr_sep* h);
+int zasr_sep_trim(zasr_sep* h);
+/* stage timing on HIP events (off by default): the milliseconds of the last call's encoder,
+   1x1 GEMMs, norms + depthwise convolution, mask + decoder in ms4[0..3] (tools/sep_bench.py) */
+int zasr_sep_set_profile(zasr_sep* h, int32_t on);
+int zasr_sep_stage_ms(zasr_sep* h, float* ms4);
+
 /* ---- device audio front end --------------------------------------------------------------
    Raw PCM -> the 16 kHz mono float32 HBM signal that zasr_decode_device,
    zasr_vad_probs_device and zasr_campp_windows_device read, and the reference's level

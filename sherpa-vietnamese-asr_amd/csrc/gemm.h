@@ -26,6 +26,8 @@ enum GemmEpi : int {
   EPI_GLU = 8,      // C[m, n / 2] = v[2c] * sigmoid(v[2c + 1]) (gemm_x3 only: the conv modules'
                     // in_proj with interleaved weight rows; N = 2 x the output width, ldc = N / 2)
   EPI_LEAKY = 9,    // C = v > 0 ? v : 0.01 v  (gemm_f32 only: the segmentation head's linears)
+  EPI_PRELU = 10,   // C = v > 0 ? v : slope * v  (gemm_f32 only: Conv-TasNet's single-slope PReLU)
+  EPI_RELUMUL = 11, // C = max(v, 0) * aux[m, n]  (gemm_f32 only: Conv-TasNet's mask on the encoder output)
 };
 
 enum GemmALoad : int {
@@ -74,6 +76,7 @@ struct GemmParams {
   const float* a_scale = nullptr;  // ALOAD_BNRELU
   const float* a_shift = nullptr;
   GemmIm2col1d i2c;                // ALOAD_IM2COL1D
+  float slope = 0.f;               // EPI_PRELU
 };
 
 // Launch; picks a tile shape from (max_M, N).  B_ncontig selects the [K][N] B layout.

@@ -206,7 +206,9 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_f32_kernel(GemmPar
         if constexpr (EPI == EPI_RELU) v = fmaxf(v, 0.f);
         if constexpr (EPI == EPI_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
         if constexpr (EPI == EPI_LEAKY) v = v > 0.f ? v : 0.01f * v;
+        if constexpr (EPI == EPI_PRELU) v = v > 0.f ? v : p.slope * v;
         if constexpr (EPI == EPI_MULAUX) v *= aux[(long)row * p.ldaux + col];
+        if constexpr (EPI == EPI_RELUMUL) v = fmaxf(v, 0.f) * aux[(long)row * p.ldaux + col];
         if constexpr (EPI == EPI_RESADD) v += *dst;
         *dst = v;
       }
@@ -929,6 +931,8 @@ void gemm_f32(const GemmParams& p, int epi, int aload, bool b_ncontig, hipStream
       case EPI_RELU: return launch_tile<ALOAD_DENSE, false, EPI_RELU>(p, st);
       case EPI_GELU: return launch_tile<ALOAD_DENSE, false, EPI_GELU>(p, st);
       case EPI_LEAKY: return launch_tile<ALOAD_DENSE, false, EPI_LEAKY>(p, st);
+      case EPI_PRELU: return launch_tile<ALOAD_DENSE, false, EPI_PRELU>(p, st);
+      case EPI_RELUMUL: return launch_tile<ALOAD_DENSE, false, EPI_RELUMUL>(p, st);
       case EPI_MULAUX: return launch_tile<ALOAD_DENSE, false, EPI_MULAUX>(p, st);
       default: break;
     }

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "diar.h"
 #include "seg.h"
+#include "sep.h"
 #include "vad.h"
 #include "vibert.h"
 #include "engine.h"
@@ -63,6 +64,10 @@ struct zasr_vad {
 
 struct zasr_seg {
   std::unique_ptr<zasr::SegEngine> eng;
+};
+
+struct zasr_sep {
+  std::unique_ptr<zasr::SepEngine> eng;
 };
 
 struct zasr_audio {
@@ -418,6 +423,109 @@ int zasr_seg_classes_device(zasr_seg* h, const float* d_audio, int64_t total,
                            reinterpret_cast<hipStream_t>(stream));
     return (int)ZASR_OK;
   });
+}
+
+// ---- Conv-TasNet overlap separation (core/overlap_separator.py) ----
+int zasr_sep_create(const char* model_dir, int32_t device_id, zasr_sep** out) {  // :45-60
+  if (!model_dir || !out) return fail(ZASR_ERR_INVALID, "null model_dir/out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_sep;
+    try {
+      h->eng.reset(new zasr::SepEngine(model_dir, device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_sep_destroy(zasr_sep* h) { delete h; }
+
+// the encoder's kernel_size; core/overlap_separator.py:291 never sees less than 0.4 s (:286-292)
+int32_t zasr_sep_min_samples(const zasr_sep* h) { return h ? h->eng->min_samples() : 0; }
+
+namespace {
+// region bounds of core/overlap_separator.py:283 (samples[s:e]), checked before the engine
+int check_sep_regions(const zasr_sep* h, int64_t total, const int64_t* starts,
+                      const int64_t* lengths, int32_t n) {
+  if (n <= 0) return fail(ZASR_ERR_INVALID, "separation: n must be positive");
+  if (!starts || !lengths || total < 0) return fail(ZASR_ERR_INVALID, "null argument");
+  for (int32_t r = 0; r < n; ++r) {
+    if (lengths[r] < h->eng->min_samples())
+      return fail(ZASR_ERR_INVALID, "separation: a region needs at least " +
+                                        std::to_string(h->eng->min_samples()) + " samples");
+    if (starts[r] < 0 || lengths[r] > total || starts[r] > total - lengths[r])
+      return fail(ZASR_ERR_INVALID, "separation: region outside the signal");
+  }
+  return ZASR_OK;
+}
+}  // namespace
+
+int zasr_sep_separate(zasr_sep* h, const float* samples, int64_t total, const int64_t* offsets,
+                      const int64_t* lengths, int32_t n, float* out) {  // :281-296
+  if (!h || !samples || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (const int rc = check_sep_regions(h, total, offsets, lengths, n)) return rc;
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->separate_host(samples, (long)total, reinterpret_cast<const long*>(offsets),
+                          reinterpret_cast<const long*>(lengths), n, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_sep_separate_device(zasr_sep* h, const float* d_audio, int64_t total,
+                             const int64_t* starts, const int64_t* lengths, int32_t n, float* out,
+                             int32_t out_on_device, void* stream) {  // :281-296
+  if (!h || !d_audio || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (const int rc = check_sep_regions(h, total, starts, lengths, n)) return rc;
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->separate_device(d_audio, (long)total, reinterpret_cast<const long*>(starts),
+                            reinterpret_cast<const long*>(lengths), n, out, out_on_device != 0,
+                            reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+// no counterpart in core/overlap_separator.py (one region per session call there, :297): the
+// bound on what the regions of one call may allocate together
+int zasr_sep_set_budget(zasr_sep* h, int64_t bytes) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  if (bytes <= 0) return fail(ZASR_ERR_INVALID, "separation: the budget must be positive");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_budget((size_t)bytes);
+  return ZASR_OK;
+}
+
+int32_t zasr_sep_last_groups(const zasr_sep* h) { return h ? h->eng->last_groups() : 0; }
+
+// core/overlap_separator.py keeps its session for the process's life (:72-73); this frees
+// the activations between files
+int zasr_sep_trim(zasr_sep* h) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->trim();
+    return (int)ZASR_OK;
+  });
+}
+
+// stage times of the call that replaces core/overlap_separator.py:297 (tools/sep_bench.py)
+int zasr_sep_set_profile(zasr_sep* h, int32_t on) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_profile(on != 0);
+  return ZASR_OK;
+}
+
+int zasr_sep_stage_ms(zasr_sep* h, float* ms4) {
+  if (!h || !ms4) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  std::memcpy(ms4, h->eng->stage_ms(), sizeof(float) * zasr::SepEngine::kStages);
+  return ZASR_OK;
 }
 
 int zasr_campp_fbank(zasr_campp* h, const float* wav, int64_t n, float* out, int64_t cap,

@@ -32,6 +32,9 @@ EXPORTS = (
     "zasr_seg_create", "zasr_seg_destroy", "zasr_seg_num_frames", "zasr_seg_logits",
     "zasr_seg_classes_device", "zasr_seg_num_chunks", "zasr_seg_last_group", "zasr_seg_set_group",
     "zasr_seg_set_profile", "zasr_seg_stage_ms", "zasr_seg_trim",
+    "zasr_sep_create", "zasr_sep_destroy", "zasr_sep_min_samples", "zasr_sep_separate",
+    "zasr_sep_separate_device", "zasr_sep_set_budget", "zasr_sep_last_groups", "zasr_sep_trim",
+    "zasr_sep_set_profile", "zasr_sep_stage_ms",
     "zasr_create_stream", "zasr_destroy_stream", "zasr_stream_accept_waveform",
     "zasr_decode_stream", "zasr_decode_streams", "zasr_stream_is_decoded",
     "zasr_stream_num_tokens", "zasr_stream_num_frames", "zasr_stream_tokens",
@@ -234,6 +237,26 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_seg_set_profile.restype = C.c_int
     lib.zasr_seg_stage_ms.argtypes = [P, fp]
     lib.zasr_seg_stage_ms.restype = C.c_int
+    lib.zasr_sep_create.argtypes = [C.c_char_p, I32, C.POINTER(P)]
+    lib.zasr_sep_create.restype = C.c_int
+    lib.zasr_sep_destroy.argtypes = [P]
+    lib.zasr_sep_destroy.restype = None
+    lib.zasr_sep_min_samples.argtypes = [P]
+    lib.zasr_sep_min_samples.restype = I32
+    lib.zasr_sep_separate.argtypes = [P, fp, I64, C.POINTER(I64), C.POINTER(I64), I32, fp]
+    lib.zasr_sep_separate.restype = C.c_int
+    lib.zasr_sep_separate_device.argtypes = [P, P, I64, C.POINTER(I64), C.POINTER(I64), I32, P, I32, P]
+    lib.zasr_sep_separate_device.restype = C.c_int
+    lib.zasr_sep_set_budget.argtypes = [P, I64]
+    lib.zasr_sep_set_budget.restype = C.c_int
+    lib.zasr_sep_last_groups.argtypes = [P]
+    lib.zasr_sep_last_groups.restype = I32
+    lib.zasr_sep_trim.argtypes = [P]
+    lib.zasr_sep_trim.restype = C.c_int
+    lib.zasr_sep_set_profile.argtypes = [P, I32]
+    lib.zasr_sep_set_profile.restype = C.c_int
+    lib.zasr_sep_stage_ms.argtypes = [P, fp]
+    lib.zasr_sep_stage_ms.restype = C.c_int
     lib.zasr_silence_flags.argtypes = [P, I64, I32, C.c_float, P, P]
     lib.zasr_silence_flags.restype = C.c_int
     # offline streams (the sherpa-onnx OfflineStream surface, zasr/offline.py)
@@ -1508,6 +1531,119 @@ class SegSession:
                 self.handle, C.c_void_p(d_audio), int(total), int(chunk_samples), int(step_samples),
                 out.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(d_logits), C.c_void_p(stream)))
         return out
+
+
+class SepSession:
+    """Conv-TasNet overlap separation on the GPU.  run(None, {"mixture": x[1, T]})
+    -> [sources [1, 2, T]] is the onnxruntime session surface the reference calls once per
+    region (core/overlap_separator.py:291); separate() takes every region of a file in one
+    call and separate_device() cuts them from the 16 kHz signal already in HBM.  A region's
+    result does not depend on the other regions of the call."""
+
+    STAGES = ("encoder", "gemms", "norms_depthwise", "mask_decoder")
+
+    def __init__(self, model_dir: str, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        rc = self.lib.zasr_sep_create(model_dir.encode(), device_id, C.byref(h))
+        if rc != 0:
+            msg = self.lib.zasr_last_error().decode()
+            if rc == 2:
+                raise FileNotFoundError(msg)
+            raise ZasrError(msg)
+        self.handle = h
+        self.min_samples = int(self.lib.zasr_sep_min_samples(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_sep_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def trim(self) -> None:
+        """Free the activation workspace the handle keeps between calls."""
+        self._check(self.lib.zasr_sep_trim(self.handle))
+
+    def set_budget(self, nbytes: int) -> None:
+        """Activation bytes one launch group may take (default 4 GiB).  Results do not change."""
+        self._check(self.lib.zasr_sep_set_budget(self.handle, int(nbytes)))
+
+    @property
+    def last_groups(self) -> int:
+        """Launch groups of the last call (diagnostic)."""
+        return int(self.lib.zasr_sep_last_groups(self.handle))
+
+    def set_profile(self, on: bool) -> None:
+        self._check(self.lib.zasr_sep_set_profile(self.handle, int(bool(on))))
+
+    def stage_ms(self) -> dict:
+        """Milliseconds of the last call's stages (after set_profile(True))."""
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zasr_sep_stage_ms(self.handle, ms))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    @staticmethod
+    def _split(flat: np.ndarray, lengths) -> List[np.ndarray]:
+        out, o = [], 0
+        for T in lengths:
+            out.append(flat[o:o + 2 * T].reshape(2, T))
+            o += 2 * T
+        return out
+
+    def separate(self, mixtures: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """Raw network output [2, T_r] (float32) of every mixture [T_r], one device call."""
+        xs = [np.ascontiguousarray(m, np.float32).reshape(-1) for m in mixtures]
+        if not xs:
+            return []
+        lengths = np.array([x.shape[0] for x in xs], np.int64)
+        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+        return self.separate_concat(np.concatenate(xs), offsets, lengths)
+
+    def separate_concat(self, samples: np.ndarray, offsets, lengths) -> List[np.ndarray]:
+        """The C entry's own form: region r = samples[offsets[r] : offsets[r] + lengths[r]]."""
+        samples = np.ascontiguousarray(samples, np.float32).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        if offsets.shape != lengths.shape:
+            raise ValueError("offsets and lengths differ in length")
+        out = np.empty(max(1, 2 * int(np.clip(lengths, 0, None).sum())), np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        self._check(self.lib.zasr_sep_separate(
+            self.handle, samples.ctypes.data_as(fp), samples.shape[0], offsets.ctypes.data_as(ip),
+            lengths.ctypes.data_as(ip), lengths.shape[0], out.ctypes.data_as(fp)))
+        return self._split(out, [int(t) for t in lengths])
+
+    def separate_device(self, d_audio: int, total: int, starts, lengths, d_out: int = 0,
+                        stream: int = 0) -> Optional[List[np.ndarray]]:
+        """Regions [starts[r], starts[r] + lengths[r]) of the signal d_audio[0, total) (a device
+        pointer).  With d_out (a device pointer to 2 * sum(lengths) float32) the result stays on
+        the device and None is returned; else the host arrays [2, T_r]."""
+        starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        if starts.shape != lengths.shape:
+            raise ValueError("starts and lengths differ in length")
+        ip = C.POINTER(C.c_int64)
+        host = None if d_out else np.empty(max(1, 2 * int(np.clip(lengths, 0, None).sum())), np.float32)
+        dst = C.c_void_p(d_out) if d_out else C.c_void_p(host.ctypes.data)
+        self._check(self.lib.zasr_sep_separate_device(
+            self.handle, C.c_void_p(d_audio), int(total), starts.ctypes.data_as(ip),
+            lengths.ctypes.data_as(ip), lengths.shape[0], dst, int(bool(d_out)), C.c_void_p(stream)))
+        return None if d_out else self._split(host, [int(t) for t in lengths])
+
+    def run(self, output_names, feeds):
+        x = np.ascontiguousarray(feeds["mixture"], np.float32)
+        if x.ndim != 2 or x.shape[0] != 1:
+            raise ZasrError("separation session: mixture [1, T]")
+        return [self.separate([x[0]])[0][None]]
 
 
 AUDIO_FORMATS = {"float32": 0, "int16": 1}  # include/zasr.h ZASR_AUDIO_F32 / ZASR_AUDIO_I16

@@ -123,11 +123,13 @@ class FullPipe:
 
     seg = None              # the segmentation session (set by __init__; None: planner regions)
     overlap_regions = None  # set by prepare() when a segmentation session is given
+    sep = None              # the separation session (set by __init__; None: no overlap segments)
+    separator = None        # its zasr.overlap.OverlapSeparator
 
     def __init__(self, rec, recd, emb, vib, vib_vocab: int, beam: int = 1,
                  campp_batch: int = 4096, iterations: int = ITERATIONS, vib_batch: int = 0,
                  tokenizer=None, confidence: float = 0.3, case_confidence: float = 0.0,
-                 shard: bool = False, diarize: bool = False, segmentation=None):
+                 shard: bool = False, diarize: bool = False, segmentation=None, separation=None):
         """diarize: cluster each pass's window embeddings into speakers (zasr.diarize: the
         reference's process() from the clustering on, :726-830) and add "speaker_segments"
         (who spoke when: [{"start", "end", "speaker"}]) and "speaker_labels" (one per window)
@@ -140,6 +142,15 @@ class FullPipe:
         _pyannote_vad, core/speaker_diarization_senko_campp_optimized.py:411-517) instead of
         the chunk planner's, region bounds int(seconds * 16000) as at :543-544, and every
         pass's dict gains "overlap_regions" ([(start_s, end_s)], :403-409).
+
+        separation: a zasr.binding.SepSession, or None (the default: nothing changes).  With a
+        session (which needs diarize=True and a segmentation session, the overlap regions and
+        the speakers it works from, and shard=False: the stage is not split over ranks) every two-speaker overlap region goes through Conv-TasNet
+        in one device call on the signal in HBM, the streams are matched to the pass's
+        speakers with CAM++ embeddings, padded with clean context and decoded again
+        (zasr.overlap: core/overlap_separator.py and core/asr_engine.py:2761-2841), and every
+        pass's dict gains "overlap_segments" (parallel {'speaker', 'speaker_id', 'start',
+        'end', 'text', 'raw_words', 'overlap': True} segments).
 
         shard: strong scaling over the ranks of an initialised torch.distributed group (one
         process per GPU, every rank given the same file): each rank decodes its
@@ -155,6 +166,16 @@ class FullPipe:
         self.seg = segmentation
         self.overlap_regions = None
         self.diar = None
+        if separation is not None and (not diarize or segmentation is None):
+            raise ValueError("separation needs diarize=True and a segmentation session")
+        if separation is not None and shard:
+            # every rank would separate and decode the same regions again: not split over ranks
+            raise ValueError("separation is not sharded: use it with shard=False")
+        self.sep = separation
+        self.separator = None
+        if separation is not None:
+            from zasr.overlap import OverlapSeparator
+            self.separator = OverlapSeparator(separation, emb)
         if diarize:
             import torch
             from zasr.binding import Diarizer
@@ -198,6 +219,7 @@ class FullPipe:
         else:
             a = np.ascontiguousarray(audio, np.float32)
         self.n = a.shape[0]
+        self.audio_host = a if self.sep is not None else None   # the separator's host logic
         plan = plan_chunks(a)                      # decode chunks, 3 s overlap
         d_early = None
         self.overlap_regions = None
@@ -324,6 +346,8 @@ class FullPipe:
                         out["overlap_regions"] = list(self.overlap_regions)
                     if self.diar is not None:
                         out["speaker_segments"], out["speaker_labels"] = self.speakers(embs, win)
+                    if self.sep is not None:
+                        out["overlap_segments"] = self.separate_overlaps(out["speaker_segments"])
                     outs.append(out)
         return outs
 
@@ -343,6 +367,21 @@ class FullPipe:
                                             k=k, N=X.shape[0], D=X.shape[1], stream=st)
         return diarize(embs, win, self.r_off_all, self.r_len_all, self.n / 16000.0, embed=embed,
                        return_labels=True)
+
+    def separate_overlaps(self, speaker_segments) -> List[Dict]:
+        """The pass's overlap segments (core/asr_engine.py:2767-2831): zasr.overlap on the
+        segmentation's overlap regions and the pass's speaker segments, the regions cut from the
+        signal in HBM, each per-speaker audio decoded by the pass's recognizer."""
+        from zasr.asr_engine import result_words
+        from zasr.overlap import overlap_segments
+        if not self.overlap_regions or not speaker_segments:
+            return []
+        self.separator.device_audio = (self.d_audio.data_ptr(), self.n)
+        results = self.separator.process(self.audio_host, speaker_segments, self.overlap_regions)
+
+        def decode(a):
+            return result_words(self.recd, self.rec.decode([a], beam=self.beam)[0], len(a), 0.0)
+        return overlap_segments(results, decode)
 
     def _gather_windows(self, embs: np.ndarray, win: np.ndarray):
         """Every rank's window embeddings and (region, first frame, frames) rows, in region
