@@ -751,6 +751,73 @@ int zasr_selftest_hotword_dfa(int32_t V, const zasr_st_hotwords* hw, int32_t cap
                               int32_t* num_states, int32_t* num_cls, int32_t* tok2cls,
                               int32_t* next, double* delta, double* node_score);
 
+/* The CAM++, Silero VAD and ViBERT kernels alone on host arrays (no reference counterpart: test
+   infrastructure; tests/test_gpu_aux_kernels.py against tests/aux_reference.py).  Each entry
+   uploads its operands, runs exactly one launch function on the null stream of device 0 (vad_frames
+   with `len`: launch_vad_maxabs first) and synchronises.  Every output is in / out: it starts as
+   the caller's image, is returned whole, and has guard bytes behind it on the device; a changed
+   guard byte returns ZASR_ERR_RUNTIME.  What a launch function refuses (Ci > 32, H > 1024,
+   L > 256, a head dim outside {16, 32, 64}) and every index that would leave an array are
+   ZASR_ERR_RUNTIME with a message before any launch.
+   campp_conv2d: launch_campp_conv2d, kernel ks (1: pad 0, 3: pad 1), stride (sf, 1), 32 output
+   channels; x [n][ci][fi][T] (in_tf: [n][T][fi], ci = 1), w [32][ci][ks][ks], scale / shift
+   [32], res nullable [n][32][fo][T], fo = (fi - 1) / sf + 1; y [n][32][fo][T], or tdnn_out
+   [n][T][32 fo].  use_mfma = 1 also passes the weights permuted by
+   campp_conv2d_permute_weights (ci = 32), so the launcher takes the MFMA kernel when its own
+   conditions hold; rb = 0: the engine's rows per block, rb > 0 (even): that many.  *route = 1
+   when the MFMA kernel ran (0: the direct kernel), *rb_used its rows per block (0: direct).
+   campp_cam_mask: h [n][T][128], w1 [64][128], b1 [64], w2 [32][64], b2 [32], mexp [n][T][32].
+   campp_stats: x [N][T][C], s / b [C], out [N][2 C] (mean | unbiased std of relu(x s + b)).
+   campp_cmvn: x [rows][80] in place, sequence i = rows [fr_off[i], fr_off[i + 1]).
+   campp_gather: rows [nrows][80], window w = rows [win_row[w], + win_n[w]) zero-padded to wf
+   frames, out [nwin][wf][80].
+   vad_frames: frames [n_windows * 4][256].  Row mode (rows576 [n_windows][576] not null): the
+   other arrays are ignored.  File mode: audio [n_samples], off / win_start [n_files] (first
+   sample / first window of each file; file f has win_start[f + 1] - win_start[f] windows); len
+   and maxabs [n_files] both null (no boost) or both given: launch_vad_maxabs fills a zeroed
+   table, which the frames kernel reads and maxabs returns.
+   vad_im2col: which 0: launch_vad_mag_im2col, in = S [N * 4][ldS] (re | im, C bins each), A
+   [N * 4][Kp]; which 1: launch_vad_im2col, in = Y [N * T][C], A [N * Tout][3 C], Tout =
+   (T - 1) / stride + 1.
+   vad_lstm: gx [windows][512], whh [512][128], bhh [512], wd [128]; segments as VadLstmArgs
+   (kernels.h): seg_start / seg_count [nseg], seg_warm nullable, init nullable [nseg][2][128];
+   probs [windows], s_out / e_out nullable [nseg][2][128].
+   vibert_ln: x [rows][H].  ids null: launch_vibert_layernorm in place.  Otherwise
+   launch_vibert_embed: ids / tt [rows], word [V][H], pos [P][H] (P >= L), type [TT][H].
+   vibert_attn: qkv [B L][3 H], mask [B L] (0 = padding), ctx [B L][H], scale 1 / sqrt(H / heads).
+   vibert_gather: x [B L][H], offsets [B][W] in [0, L), g [B W][H]. */
+int zasr_selftest_campp_conv2d(int32_t ks, int32_t ci, int32_t fi, int32_t sf, int32_t T, int32_t n,
+                               int32_t relu, int32_t tdnn_out, int32_t in_tf, int32_t use_mfma,
+                               int32_t rb, const float* x, const float* w, const float* scale,
+                               const float* shift, const float* res, float* y, int32_t* route,
+                               int32_t* rb_used);
+int zasr_selftest_campp_cam_mask(int32_t n, int32_t T, int32_t seg_len, const float* h,
+                                 const float* w1, const float* b1, const float* w2,
+                                 const float* b2, float* mexp);
+int zasr_selftest_campp_stats(int32_t N, int32_t T, int32_t C, const float* x, const float* s,
+                              const float* b, float* out);
+int zasr_selftest_campp_cmvn(int32_t nseq, int32_t rows, const int32_t* fr_off, float* x);
+int zasr_selftest_campp_gather(int32_t nwin, int32_t wf, int32_t nrows, const float* rows,
+                               const int32_t* win_row, const int32_t* win_n, float* out);
+int zasr_selftest_vad_frames(int32_t n_files, int64_t n_windows, int64_t n_samples,
+                             const float* audio, const int64_t* off, const int64_t* win_start,
+                             const int64_t* len, const float* rows576, uint32_t* maxabs,
+                             float* frames);
+int zasr_selftest_vad_im2col(int32_t which, int64_t N, int32_t T, int32_t C, int32_t stride,
+                             int32_t ldS, int32_t Kp, const float* in, float* A);
+int zasr_selftest_vad_lstm(int64_t windows, int32_t nseg, const float* gx, const float* whh,
+                           const float* bhh, const float* wd, float bd, const int64_t* seg_start,
+                           const int32_t* seg_count, const int32_t* seg_warm, const float* init,
+                           float* probs, float* s_out, float* e_out);
+int zasr_selftest_vibert_ln(int64_t rows, int32_t H, int32_t L, const int64_t* ids,
+                            const int64_t* tt, int32_t V, int32_t P, int32_t TT, const float* word,
+                            const float* pos, const float* type, const float* g, const float* b,
+                            float eps, float* x);
+int zasr_selftest_vibert_attn(int32_t B, int32_t L, int32_t heads, int32_t H, const float* qkv,
+                              const int64_t* mask, float* ctx);
+int zasr_selftest_vibert_gather(int32_t B, int32_t L, int32_t W, int32_t H, const float* x,
+                                const int64_t* offsets, float* g);
+
 /* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
    core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the
    eigenvectors; the eigengap rule, k-means and the segment logic are host code in

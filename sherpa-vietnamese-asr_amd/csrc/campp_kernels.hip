@@ -304,15 +304,16 @@ void campp_conv2d_permute_weights(const float* w, int ks, float* out) {
 }
 
 void launch_campp_conv2d(const CamppConv2d& a, int ks, hipStream_t st) {
+  launch_campp_conv2d(a, ks, campp_conv2d_rows_per_block(a.fo, a.n), st);
+}
+
+int launch_campp_conv2d(const CamppConv2d& a, int ks, int rb, hipStream_t st) {
   ZASR_REQUIRE(a.ci <= 32 && (ks == 1 || ks == 3), "campp conv2d: Ci <= 32, kernel 1 or 3");
   // the 3 x 3 convolutions take the MFMA kernel; the 1 x 1 shortcut (a quarter of the
   // rows' work, no reuse across taps) stays on the direct kernel, which measured faster
   if (ks == 3 && a.wk && a.ci == 32 && !a.in_tf && a.T <= 160 &&
       (a.sf == 1 || a.sf == 2)) {
-    // rows per block: about 2048 blocks per launch, an even row count, at least 2
-    const int pairs = cdiv(a.fo, 2);
-    const int chunks = std::max(1, std::min(pairs, cdiv(2048, a.n)));
-    const int rb = 2 * cdiv(pairs, chunks);
+    ZASR_REQUIRE(rb >= 2 && rb % 2 == 0, "campp conv2d: rows per block even, at least 2");
     const dim3 grid(cdiv(a.fo, rb), a.n);
 #define ZASR_CX(KSV, SFV, RESV) \
   ZASR_LAUNCH((campp_conv2d_mfma_kernel<KSV, SFV, RESV>), grid, dim3(256), 0, st, a, rb)
@@ -321,12 +322,13 @@ void launch_campp_conv2d(const CamppConv2d& a, int ks, hipStream_t st) {
     else if (a.res) ZASR_CX(3, 2, true);
     else ZASR_CX(3, 2, false);
 #undef ZASR_CX
-    return;
+    return rb;
   }
   dim3 grid(cdiv(a.T, 64), a.fo, a.n);
   if (ks == 3 && a.ci == 1) ZASR_LAUNCH((campp_conv2d_kernel<3, 1>), grid, dim3(256), 0, st, a);
   else if (ks == 3) ZASR_LAUNCH((campp_conv2d_kernel<3, 32>), grid, dim3(256), 0, st, a);
   else ZASR_LAUNCH((campp_conv2d_kernel<1, 32>), grid, dim3(256), 0, st, a);
+  return 0;
 }
 
 // CAM context mask (CAMLayer.forward: context = mean_t(x) + seg_pooling(x); m = sigmoid(

@@ -71,6 +71,36 @@ void selftest_ffn_bf16(int R, int D, int F, const float* W1, const float* b1, co
 // Xout (nullable): out of place -- the kernel reads X, writes Xout (on entry the buffer's
 // initial contents); X returns what its buffer holds afterwards.  ffn_h3: Y must be null.
 
+// the CAM++, Silero VAD and ViBERT kernels alone, one launch function per entry (selftest.cpp;
+// include/zasr.h zasr_selftest_campp_* / _vad_* / _vibert_*): every output in / out, guarded
+void selftest_campp_conv2d(int ks, int ci, int fi, int sf, int T, int n, int relu, int tdnn_out,
+                           int in_tf, int use_mfma, int rb, const float* x, const float* w,
+                           const float* scale, const float* shift, const float* res, float* y,
+                           int* route, int* rb_used);
+void selftest_campp_cam_mask(int n, int T, int seg_len, const float* h, const float* w1,
+                             const float* b1, const float* w2, const float* b2, float* mexp);
+void selftest_campp_stats(int N, int T, int C, const float* x, const float* s, const float* b,
+                          float* out);
+void selftest_campp_cmvn(int nseq, int rows, const int* fr_off, float* x);
+void selftest_campp_gather(int nwin, int wf, int nrows, const float* rows, const int* win_row,
+                           const int* win_n, float* out);
+void selftest_vad_frames(int n_files, long n_windows, long n_samples, const float* audio,
+                         const long* off, const long* win_start, const long* len,
+                         const float* rows576, unsigned* maxabs, float* frames);
+void selftest_vad_im2col(int which, long N, int T, int C, int stride, int ldS, int Kp,
+                         const float* in, float* A);
+void selftest_vad_lstm(long windows, int nseg, const float* gx, const float* whh, const float* bhh,
+                       const float* wd, float bd, const long* seg_start, const int* seg_count,
+                       const int* seg_warm, const float* init, float* probs, float* s_out,
+                       float* e_out);
+void selftest_vibert_ln(long rows, int H, int L, const long* ids, const long* tt, int V, int P,
+                        int TT, const float* word, const float* pos, const float* type,
+                        const float* g, const float* b, float eps, float* x);
+void selftest_vibert_attn(int B, int L, int heads, int H, const float* qkv, const long* mask,
+                          float* ctx);
+void selftest_vibert_gather(int B, int L, int W, int H, const float* x, const long* offsets,
+                            float* g);
+
 // ---- CAM++ speaker embedding (campp_kernels.hip) ----
 struct CamppConv2d {
   const float* x;      // [n][ci][fi][T]
@@ -85,7 +115,16 @@ struct CamppConv2d {
   const float* wk = nullptr;  // ci = 32: weights permuted by campp_conv2d_permute_weights
 };
 void campp_conv2d_permute_weights(const float* w, int ks, float* out);
+// rows per block of the MFMA kernel: about 2048 blocks per launch, an even row count, at least 2
+inline int campp_conv2d_rows_per_block(int fo, int n) {
+  const int pairs = (fo + 1) / 2, want = (2048 + n - 1) / n;
+  const int chunks = want < pairs ? (want > 1 ? want : 1) : (pairs > 1 ? pairs : 1);
+  return 2 * ((pairs + chunks - 1) / chunks);
+}
 void launch_campp_conv2d(const CamppConv2d& a, int ks, hipStream_t st);
+// the same with the MFMA kernel's rows per block given (even, >= 2; the self-test's override);
+// returns the rows per block of the MFMA kernel, or 0 when the direct kernel ran
+int launch_campp_conv2d(const CamppConv2d& a, int ks, int rb, hipStream_t st);
 struct CamppCamMask {
   const float* h;      // [n * T][128] CAM input (nonlinear2 output)
   const float* w1;     // [64][128] linear1

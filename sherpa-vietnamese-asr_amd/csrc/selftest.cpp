@@ -8,9 +8,11 @@
 // the joiner kernels on row-major and on host-packed J, and the transducer search kernels (one
 // frame, one greedy window, the final pick) on a caller-supplied search state, and the general
 // GEMMs behind their implicit-im2col and BN-ReLU operand loaders (conv.4 / conv.7 over one
-// z-slice per sequence as a decode launches them; the CAM++ projections of gemm_f32).
+// z-slice per sequence as a decode launches them; the CAM++ projections of gemm_f32), and the
+// CAM++, Silero VAD and ViBERT kernels, one launch function per entry.
 // Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -1346,6 +1348,285 @@ void selftest_gemm_aload(int aload, int M, int K, int N, int lda, int ldc, int c
   gemm_f32(p, epi, aload, false, nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   o.down(C, "gemm_aload");
+}
+
+// ---- the CAM++, Silero VAD and ViBERT kernels ----
+namespace {
+constexpr size_t kAuxMax = (size_t)1 << 27;  // elements of any one array of these entries
+
+// an input of n elements of T on the device (n = 0 or a null host pointer: a 4-byte allocation)
+template <class T>
+struct DevIn {
+  DevBuf d;
+  DevIn(const T* h, size_t n) : d(n * sizeof(T)) {
+    if (h) up(d, h, n * sizeof(T));
+  }
+  const T* p() const { return d.as<T>(); }
+};
+}  // namespace
+
+void selftest_campp_conv2d(int ks, int ci, int fi, int sf, int T, int n, int relu, int tdnn_out,
+                           int in_tf, int use_mfma, int rb, const float* x, const float* w,
+                           const float* scale, const float* shift, const float* res, float* y,
+                           int* route, int* rb_used) {
+  const std::string m = "selftest campp_conv2d: ";
+  ZASR_REQUIRE(ks == 1 || ks == 3, m + "kernel 1 or 3");
+  ZASR_REQUIRE(ci >= 1 && ci <= 1024, m + "Ci out of range");  // the launch refuses Ci > 32
+  ZASR_REQUIRE(fi >= 1 && fi <= 1024 && T >= 1 && T <= 4096 && n >= 1 && n <= 65535 && sf >= 1 && sf <= 8,
+               m + "sizes out of range");
+  ZASR_REQUIRE(!in_tf || ci == 1, m + "the [n][T][fi] input form is the Ci = 1 convolution's");
+  ZASR_REQUIRE(rb >= 0 && rb % 2 == 0, m + "rb 0 (the engine's pick) or even");
+  ZASR_REQUIRE(!use_mfma || ci == 32, m + "the permuted weights are the Ci = 32 convolutions'");
+  const int fo = (fi - 1) / sf + 1;
+  const size_t nx = (size_t)n * ci * fi * T, nw = (size_t)32 * ci * ks * ks, ny = (size_t)n * 32 * fo * T;
+  ZASR_REQUIRE(nx <= kAuxMax && ny <= kAuxMax, m + "problem too large");
+  std::vector<float> pk(use_mfma ? nw : 0);
+  if (use_mfma) campp_conv2d_permute_weights(w, ks, pk.data());
+  DevIn<float> dX(x, nx), dW(w, nw), dK(pk.data(), pk.size()), dSc(scale, 32), dSh(shift, 32),
+      dR(res, res ? ny : 0);
+  GuardedOut o(y, ny * 4);
+  CamppConv2d a{};
+  a.x = dX.p();
+  a.w = dW.p();
+  a.scale = dSc.p();
+  a.shift = dSh.p();
+  a.res = res ? dR.p() : nullptr;
+  a.y = o.d.as<float>();
+  a.n = n;
+  a.ci = ci;
+  a.fi = fi;
+  a.fo = fo;
+  a.T = T;
+  a.sf = sf;
+  a.relu = relu;
+  a.tdnn_out = tdnn_out;
+  a.in_tf = in_tf;
+  a.wk = use_mfma ? dK.p() : nullptr;
+  const int used = launch_campp_conv2d(a, ks, rb ? rb : campp_conv2d_rows_per_block(fo, n), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(y, "campp_conv2d");
+  *route = used ? 1 : 0;
+  *rb_used = used;
+}
+
+void selftest_campp_cam_mask(int n, int T, int seg_len, const float* h, const float* w1,
+                             const float* b1, const float* w2, const float* b2, float* mexp) {
+  ZASR_REQUIRE(n >= 1 && n <= 65535 && T >= 1 && seg_len >= 1 && (size_t)n * T * 128 <= kAuxMax,
+               "selftest campp_cam_mask: sizes out of range");
+  DevIn<float> dH(h, (size_t)n * T * 128), d1(w1, 64 * 128), dB1(b1, 64), d2(w2, 32 * 64), dB2(b2, 32);
+  GuardedOut o(mexp, (size_t)n * T * 32 * 4);
+  CamppCamMask a{dH.p(), d1.p(), dB1.p(), d2.p(), dB2.p(), o.d.as<float>(), n, T, seg_len};
+  launch_campp_cam_mask(a, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(mexp, "campp_cam_mask");
+}
+
+void selftest_campp_stats(int N, int T, int C, const float* x, const float* s, const float* b,
+                          float* out) {
+  ZASR_REQUIRE(N >= 1 && T >= 1 && C >= 1 && (size_t)N * T * C <= kAuxMax,
+               "selftest campp_stats: sizes out of range");
+  DevIn<float> dX(x, (size_t)N * T * C), dS(s, C), dB(b, C);
+  GuardedOut o(out, (size_t)N * 2 * C * 4);
+  launch_campp_stats(dX.p(), N, T, C, dS.p(), dB.p(), o.d.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(out, "campp_stats");
+}
+
+void selftest_campp_cmvn(int nseq, int rows, const int* fr_off, float* x) {
+  const std::string m = "selftest campp_cmvn: ";
+  ZASR_REQUIRE(nseq >= 1 && nseq <= 65535 && rows >= 0 && (size_t)rows * 80 <= kAuxMax, m + "sizes out of range");
+  ZASR_REQUIRE(fr_off[0] >= 0 && fr_off[nseq] <= rows, m + "the sequences must lie inside the rows");
+  for (int s = 0; s < nseq; ++s) ZASR_REQUIRE(fr_off[s] <= fr_off[s + 1], m + "offsets must not decrease");
+  DevIn<int> dO(fr_off, (size_t)nseq + 1);
+  GuardedOut o(x, (size_t)rows * 80 * 4);
+  launch_campp_cmvn(o.d.as<float>(), dO.p(), nseq, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(x, "campp_cmvn");
+}
+
+void selftest_campp_gather(int nwin, int wf, int nrows, const float* rows, const int* win_row,
+                           const int* win_n, float* out) {
+  const std::string m = "selftest campp_gather: ";
+  ZASR_REQUIRE(nwin >= 1 && wf >= 1 && nrows >= 1 && (size_t)nwin * wf * 80 <= kAuxMax &&
+                   (size_t)nrows * 80 <= kAuxMax, m + "sizes out of range");
+  for (int w = 0; w < nwin; ++w)
+    ZASR_REQUIRE(win_row[w] >= 0 && win_n[w] >= 0 && win_n[w] <= wf && (long)win_row[w] + win_n[w] <= nrows,
+                 m + "every window's rows must lie inside the packed rows, at most wf of them");
+  DevIn<float> dR(rows, (size_t)nrows * 80);
+  DevIn<int> dW(win_row, nwin), dN(win_n, nwin);
+  GuardedOut o(out, (size_t)nwin * wf * 80 * 4);
+  launch_campp_gather(dR.p(), dW.p(), dN.p(), nwin, wf, o.d.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(out, "campp_gather");
+}
+
+void selftest_vad_frames(int n_files, long n_windows, long n_samples, const float* audio,
+                         const long* off, const long* win_start, const long* len,
+                         const float* rows576, unsigned* maxabs, float* frames) {
+  const std::string m = "selftest vad_frames: ";
+  ZASR_REQUIRE(n_windows >= 1 && (size_t)n_windows * 1024 <= kAuxMax, m + "window count out of range");
+  GuardedOut o(frames, (size_t)n_windows * 1024 * 4);
+  VadFramesArgs a{};
+  a.frames = o.d.as<float>();
+  if (rows576) {
+    DevIn<float> dR(rows576, (size_t)n_windows * 576);
+    a.rows576 = dR.p();
+    launch_vad_frames(a, n_windows, nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    o.down(frames, "vad_frames");
+    return;
+  }
+  ZASR_REQUIRE(audio && off && win_start, m + "the file mode takes audio, off and win_start");
+  ZASR_REQUIRE(n_files >= 1 && n_files <= 65535 && n_samples >= 1 && (size_t)n_samples <= kAuxMax,
+               m + "sizes out of range");
+  ZASR_REQUIRE((len == nullptr) == (maxabs == nullptr), m + "len and maxabs go together");
+  ZASR_REQUIRE(win_start[0] == 0, m + "the first file starts at window 0");
+  for (int f = 0; f < n_files; ++f) {
+    const long next = f + 1 < n_files ? win_start[f + 1] : n_windows;
+    ZASR_REQUIRE(next >= win_start[f] && next <= n_windows, m + "win_start must not decrease");
+    ZASR_REQUIRE(off[f] >= 0 && off[f] + (next - win_start[f]) * 512 <= n_samples,
+                 m + "every file's windows must lie inside the audio");
+    ZASR_REQUIRE(!len || (len[f] >= 0 && off[f] + len[f] <= n_samples), m + "every file must lie inside the audio");
+  }
+  DevIn<float> dA(audio, (size_t)n_samples);
+  DevIn<long> dO(off, n_files), dS(win_start, n_files), dL(len, len ? n_files : 0);
+  GuardedOut mx(std::vector<unsigned>(n_files, 0u).data(), (size_t)n_files * 4);
+  a.audio = dA.p();
+  a.off = dO.p();
+  a.win_start = dS.p();
+  a.n_files = n_files;
+  if (len) {
+    launch_vad_maxabs(dA.p(), dO.p(), dL.p(), n_files, mx.d.as<unsigned>(), nullptr);
+    a.maxabs = mx.d.as<unsigned>();
+  }
+  launch_vad_frames(a, n_windows, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(frames, "vad_frames");
+  if (len) mx.down(maxabs, "vad_frames (maxabs)");
+}
+
+void selftest_vad_im2col(int which, long N, int T, int C, int stride, int ldS, int Kp,
+                         const float* in, float* A) {
+  const std::string m = "selftest vad_im2col: ";
+  ZASR_REQUIRE(which == 0 || which == 1, m + "which 0 (mag_im2col) or 1 (im2col)");
+  ZASR_REQUIRE(N >= 1 && N <= (1 << 20) && C >= 1 && C <= 4096, m + "sizes out of range");
+  if (which == 0) {  // N windows of 4 STFT rows (re | im), C bins
+    ZASR_REQUIRE(ldS >= 2 * C && ldS <= 16384 && Kp >= 1 && Kp <= 16384, m + "ldS >= 2 bins, Kp >= 1");
+    ZASR_REQUIRE((size_t)N * 4 * ldS <= kAuxMax && (size_t)N * 4 * Kp <= kAuxMax, m + "problem too large");
+    DevIn<float> dS(in, (size_t)N * 4 * ldS);
+    GuardedOut o(A, (size_t)N * 4 * Kp * 4);
+    launch_vad_mag_im2col(dS.p(), ldS, C, Kp, N, o.d.as<float>(), nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    o.down(A, "vad_im2col");
+    return;
+  }
+  ZASR_REQUIRE(T >= 1 && T <= 4096 && stride >= 1 && stride <= 64, m + "T / stride out of range");
+  const int Tout = (T - 1) / stride + 1;
+  ZASR_REQUIRE((size_t)N * T * C <= kAuxMax && (size_t)N * Tout * 3 * C <= kAuxMax, m + "problem too large");
+  DevIn<float> dY(in, (size_t)N * T * C);
+  GuardedOut o(A, (size_t)N * Tout * 3 * C * 4);
+  launch_vad_im2col(dY.p(), N, T, C, stride, Tout, o.d.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(A, "vad_im2col");
+}
+
+void selftest_vad_lstm(long windows, int nseg, const float* gx, const float* whh, const float* bhh,
+                       const float* wd, float bd, const long* seg_start, const int* seg_count,
+                       const int* seg_warm, const float* init, float* probs, float* s_out,
+                       float* e_out) {
+  const std::string m = "selftest vad_lstm: ";
+  ZASR_REQUIRE(windows >= 1 && windows <= (1 << 16) && nseg >= 1 && nseg <= 4096, m + "sizes out of range");
+  for (int s = 0; s < nseg; ++s) {
+    const int warm = seg_warm ? seg_warm[s] : 0;
+    ZASR_REQUIRE(warm >= 0 && seg_count[s] >= 0 && seg_start[s] - warm >= 0 &&
+                     seg_start[s] + seg_count[s] <= windows,
+                 m + "every segment, its warm-up included, must lie inside the windows");
+  }
+  const size_t ns = (size_t)nseg * 256;
+  DevIn<float> dG(gx, (size_t)windows * 512), dW(whh, 512 * 128), dB(bhh, 512), dD(wd, 128),
+      dI(init, init ? ns : 0);
+  DevIn<long> dS(seg_start, nseg);
+  DevIn<int> dC(seg_count, nseg), dWm(seg_warm, seg_warm ? nseg : 0);
+  GuardedOut op(probs, (size_t)windows * 4);
+  std::unique_ptr<GuardedOut> os, oe;
+  if (s_out) os.reset(new GuardedOut(s_out, ns * 4));
+  if (e_out) oe.reset(new GuardedOut(e_out, ns * 4));
+  VadLstmArgs a{};
+  a.gx = dG.p();
+  a.whh = dW.p();
+  a.bhh = dB.p();
+  a.wd = dD.p();
+  a.bd = bd;
+  a.seg_start = dS.p();
+  a.seg_count = dC.p();
+  a.seg_warm = seg_warm ? dWm.p() : nullptr;
+  a.init = init ? dI.p() : nullptr;
+  a.s_out = os ? os->d.as<float>() : nullptr;
+  a.e_out = oe ? oe->d.as<float>() : nullptr;
+  a.probs = op.d.as<float>();
+  launch_vad_lstm(a, nseg, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  op.down(probs, "vad_lstm");
+  if (os) os->down(s_out, "vad_lstm");
+  if (oe) oe->down(e_out, "vad_lstm");
+}
+
+void selftest_vibert_ln(long rows, int H, int L, const long* ids, const long* tt, int V, int P,
+                        int TT, const float* word, const float* pos, const float* type,
+                        const float* g, const float* b, float eps, float* x) {
+  const std::string m = "selftest vibert_ln: ";
+  ZASR_REQUIRE(rows >= 1 && rows <= (1 << 20) && H >= 1 && H <= (1 << 16) && (size_t)rows * H <= kAuxMax,
+               m + "sizes out of range");
+  DevIn<float> dG(g, H), dB(b, H);
+  GuardedOut o(x, (size_t)rows * H * 4);
+  if (!ids) {
+    launch_vibert_layernorm(o.d.as<float>(), rows, H, dG.p(), dB.p(), eps, nullptr);
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    o.down(x, "vibert_ln");
+    return;
+  }
+  ZASR_REQUIRE(tt && word && pos && type, m + "the embedding form takes ids, tt and the three tables");
+  ZASR_REQUIRE(L >= 1 && V >= 1 && TT >= 1 && P >= L && (size_t)V * H <= kAuxMax && (size_t)P * H <= kAuxMax,
+               m + "table sizes out of range (the position table needs L rows)");
+  for (long r = 0; r < rows; ++r)
+    ZASR_REQUIRE(ids[r] >= 0 && ids[r] < V && tt[r] >= 0 && tt[r] < TT, m + "ids / token types outside their tables");
+  DevIn<long> dI(ids, rows), dT(tt, rows);
+  DevIn<float> dW(word, (size_t)V * H), dP(pos, (size_t)P * H), dY(type, (size_t)TT * H);
+  VibertEmbedArgs a{dI.p(), dT.p(), dW.p(), dP.p(), dY.p(), dG.p(), dB.p(), o.d.as<float>(), L, H, eps};
+  launch_vibert_embed(a, rows, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(x, "vibert_ln");
+}
+
+void selftest_vibert_attn(int B, int L, int heads, int H, const float* qkv, const long* mask,
+                          float* ctx) {
+  const std::string m = "selftest vibert_attn: ";
+  ZASR_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && L <= (1 << 16) && heads >= 1 && heads <= 1024 && H >= 1 &&
+                   H <= (1 << 16) && (size_t)B * L * 3 * H <= kAuxMax, m + "sizes out of range");
+  const size_t R = (size_t)B * L;
+  DevIn<float> dQ(qkv, R * 3 * H);
+  DevIn<long> dM(mask, R);
+  GuardedOut o(ctx, R * H * 4);
+  const int D = H / heads;
+  VibertAttnArgs a{dQ.p(), dM.p(), o.d.as<float>(), L, H, 1.f / std::sqrt((float)(D > 0 ? D : 1))};
+  launch_vibert_attention(a, B, heads, nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(ctx, "vibert_attn");
+}
+
+void selftest_vibert_gather(int B, int L, int W, int H, const float* x, const long* offsets,
+                            float* g) {
+  const std::string m = "selftest vibert_gather: ";
+  ZASR_REQUIRE(B >= 1 && L >= 1 && W >= 1 && H >= 1 && (size_t)B * L * H <= kAuxMax &&
+                   (size_t)B * W * H <= kAuxMax, m + "sizes out of range");
+  for (long i = 0; i < (long)B * W; ++i)
+    ZASR_REQUIRE(offsets[i] >= 0 && offsets[i] < L, m + "offsets must lie inside the sequence");
+  DevIn<float> dX(x, (size_t)B * L * H);
+  DevIn<long> dO(offsets, (size_t)B * W);
+  GuardedOut o(g, (size_t)B * W * H * 4);
+  launch_vibert_gather(dX.p(), dO.p(), B, L, W, H, o.d.as<float>(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(g, "vibert_gather");
 }
 
 }  // namespace zasr

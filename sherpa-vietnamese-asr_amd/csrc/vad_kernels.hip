@@ -25,6 +25,17 @@ __device__ __forceinline__ int window_file(const long* win_start, int n_files, l
   }
   return lo;
 }
+
+// sqrt(re^2 + im^2) in step-wise IEEE f32, as numpy computes it: the sum must not contract
+// into an fma, and the root is sqrtf (correctly rounded).  The __fmul_rn / __fadd_rn /
+// __fsqrt_rn intrinsics give neither without OCML_BASIC_ROUNDED_OPERATIONS: the first two are
+// plain operators the compiler may contract, the last is the native 1-ulp root.
+__device__ __forceinline__ float vad_mag(float re, float im) {
+#pragma clang fp contract(off)
+  const float rr = re * re;
+  const float ii = im * im;
+  return sqrtf(rr + ii);
+}
 }  // namespace
 
 // per-file max |x| as float bits (non-negative floats order like their bit patterns)
@@ -86,8 +97,7 @@ __global__ void vad_mag_im2col_kernel(const float* __restrict__ S, int ldS, int 
       const int k = i / bins, c = i - k * bins, tt = t + k - 1;
       if (tt >= 0 && tt < VFR) {
         const float* s = S + (g * VFR + tt) * ldS;
-        const float re = s[c], im = s[bins + c];
-        v = __fsqrt_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));
+        v = vad_mag(s[c], s[bins + c]);
       }
     }
     dst[i] = v;

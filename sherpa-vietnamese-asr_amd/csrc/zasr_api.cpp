@@ -922,6 +922,119 @@ int zasr_selftest_gemm_aload(int32_t aload, int32_t M, int32_t K, int32_t N, int
   });
 }
 
+int zasr_selftest_campp_conv2d(int32_t ks, int32_t ci, int32_t fi, int32_t sf, int32_t T, int32_t n,
+                               int32_t relu, int32_t tdnn_out, int32_t in_tf, int32_t use_mfma,
+                               int32_t rb, const float* x, const float* w, const float* scale,
+                               const float* shift, const float* res, float* y, int32_t* route,
+                               int32_t* rb_used) {
+  if (!x || !w || !scale || !shift || !y || !route || !rb_used)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_campp_conv2d(ks, ci, fi, sf, T, n, relu, tdnn_out, in_tf, use_mfma, rb, x, w,
+                                scale, shift, res, y, route, rb_used);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_campp_cam_mask(int32_t n, int32_t T, int32_t seg_len, const float* h,
+                                 const float* w1, const float* b1, const float* w2,
+                                 const float* b2, float* mexp) {
+  if (!h || !w1 || !b1 || !w2 || !b2 || !mexp) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_campp_cam_mask(n, T, seg_len, h, w1, b1, w2, b2, mexp);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_campp_stats(int32_t N, int32_t T, int32_t C, const float* x, const float* s,
+                              const float* b, float* out) {
+  if (!x || !s || !b || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_campp_stats(N, T, C, x, s, b, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_campp_cmvn(int32_t nseq, int32_t rows, const int32_t* fr_off, float* x) {
+  if (!fr_off || !x) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_campp_cmvn(nseq, rows, fr_off, x);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_campp_gather(int32_t nwin, int32_t wf, int32_t nrows, const float* rows,
+                               const int32_t* win_row, const int32_t* win_n, float* out) {
+  if (!rows || !win_row || !win_n || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_campp_gather(nwin, wf, nrows, rows, win_row, win_n, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vad_frames(int32_t n_files, int64_t n_windows, int64_t n_samples,
+                             const float* audio, const int64_t* off, const int64_t* win_start,
+                             const int64_t* len, const float* rows576, uint32_t* maxabs,
+                             float* frames) {
+  if (!frames) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vad_frames(n_files, n_windows, n_samples, audio, off, win_start, len, rows576,
+                              maxabs, frames);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vad_im2col(int32_t which, int64_t N, int32_t T, int32_t C, int32_t stride,
+                             int32_t ldS, int32_t Kp, const float* in, float* A) {
+  if (!in || !A) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vad_im2col(which, N, T, C, stride, ldS, Kp, in, A);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vad_lstm(int64_t windows, int32_t nseg, const float* gx, const float* whh,
+                           const float* bhh, const float* wd, float bd, const int64_t* seg_start,
+                           const int32_t* seg_count, const int32_t* seg_warm, const float* init,
+                           float* probs, float* s_out, float* e_out) {
+  if (!gx || !whh || !bhh || !wd || !seg_start || !seg_count || !probs)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vad_lstm(windows, nseg, gx, whh, bhh, wd, bd, seg_start, seg_count, seg_warm,
+                            init, probs, s_out, e_out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vibert_ln(int64_t rows, int32_t H, int32_t L, const int64_t* ids,
+                            const int64_t* tt, int32_t V, int32_t P, int32_t TT, const float* word,
+                            const float* pos, const float* type, const float* g, const float* b,
+                            float eps, float* x) {
+  if (!g || !b || !x) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vibert_ln(rows, H, L, ids, tt, V, P, TT, word, pos, type, g, b, eps, x);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vibert_attn(int32_t B, int32_t L, int32_t heads, int32_t H, const float* qkv,
+                              const int64_t* mask, float* ctx) {
+  if (!qkv || !mask || !ctx) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vibert_attn(B, L, heads, H, qkv, mask, ctx);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_vibert_gather(int32_t B, int32_t L, int32_t W, int32_t H, const float* x,
+                                const int64_t* offsets, float* g) {
+  if (!x || !offsets || !g) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_vibert_gather(B, L, W, H, x, offsets, g);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int32_t D,
                          const float* J, const float* W, const float* bias,
                          const int32_t* live_t, const int32_t* live_len, int32_t live_f,

@@ -49,6 +49,10 @@ EXPORTS = (
     "zasr_selftest_bias_norm", "zasr_selftest_attn_weights", "zasr_selftest_attn_sa",
     "zasr_selftest_nonlin", "zasr_selftest_search_step", "zasr_selftest_greedy_spec",
     "zasr_selftest_search_final", "zasr_selftest_hotword_dfa",
+    "zasr_selftest_campp_conv2d", "zasr_selftest_campp_cam_mask", "zasr_selftest_campp_stats",
+    "zasr_selftest_campp_cmvn", "zasr_selftest_campp_gather", "zasr_selftest_vad_frames",
+    "zasr_selftest_vad_im2col", "zasr_selftest_vad_lstm", "zasr_selftest_vibert_ln",
+    "zasr_selftest_vibert_attn", "zasr_selftest_vibert_gather",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -341,6 +345,24 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_hotword_dfa.argtypes = [I32, hp, I32, ip32, ip32, ip32, ip32,
                                               C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.zasr_selftest_hotword_dfa.restype = C.c_int
+    ip64 = C.POINTER(I64)
+    lib.zasr_selftest_campp_conv2d.argtypes = [I32] * 11 + [fp] * 6 + [ip32, ip32]
+    lib.zasr_selftest_campp_cam_mask.argtypes = [I32] * 3 + [fp] * 6
+    lib.zasr_selftest_campp_stats.argtypes = [I32] * 3 + [fp] * 4
+    lib.zasr_selftest_campp_cmvn.argtypes = [I32, I32, ip32, fp]
+    lib.zasr_selftest_campp_gather.argtypes = [I32, I32, I32, fp, ip32, ip32, fp]
+    lib.zasr_selftest_vad_frames.argtypes = [I32, I64, I64, fp, ip64, ip64, ip64, fp,
+                                             C.POINTER(C.c_uint32), fp]
+    lib.zasr_selftest_vad_im2col.argtypes = [I32, I64] + [I32] * 5 + [fp, fp]
+    lib.zasr_selftest_vad_lstm.argtypes = [I64, I32, fp, fp, fp, fp, C.c_float, ip64, ip32, ip32,
+                                           fp, fp, fp, fp]
+    lib.zasr_selftest_vibert_ln.argtypes = [I64, I32, I32, ip64, ip64, I32, I32, I32] + [fp] * 5 + [
+        C.c_float, fp]
+    lib.zasr_selftest_vibert_attn.argtypes = [I32] * 4 + [fp, ip64, fp]
+    lib.zasr_selftest_vibert_gather.argtypes = [I32] * 4 + [fp, ip64, fp]
+    for _n in ("campp_conv2d", "campp_cam_mask", "campp_stats", "campp_cmvn", "campp_gather",
+               "vad_frames", "vad_im2col", "vad_lstm", "vibert_ln", "vibert_attn", "vibert_gather"):
+        getattr(lib, "zasr_selftest_" + _n).restype = C.c_int
     # device audio front end (zasr/audio.py)
     lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
     lib.zasr_audio_create.restype = C.c_int
@@ -932,6 +954,212 @@ def selftest_bias_norm(x, bias, log_scale: float, orig=None, bscale=None, copy_m
     if rc != 0:
         raise ZasrError(lib.zasr_last_error().decode())
     return {"x": x, "orig": o, "copy": cp}
+
+
+# ---- the CAM++, Silero VAD and ViBERT kernels alone (include/zasr.h zasr_selftest_campp_* /
+# _vad_* / _vibert_*).  Every returned array started as `fill` (or as the given image).
+def _aux_ptr(a, t=None):
+    return None if a is None else a.ctypes.data_as(C_FP if t is None else C.POINTER(t))
+
+
+def _aux_check(lib, rc):
+    if rc != 0:
+        raise ZasrError(lib.zasr_last_error().decode())
+
+
+def _i64(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def selftest_campp_conv2d(x, w, scale, shift, res=None, *, ks: int, ci: int, fi: int, sf: int, T: int,
+                          n: int, relu: bool, tdnn_out: bool, in_tf: bool, use_mfma: bool,
+                          rb: int = 0, fill: float = -777.25, lib_path: Optional[str] = None):
+    """launch_campp_conv2d alone: returns (y [n][32][fo][T] or, tdnn_out, [n][T][32 fo]; route
+    (1: the MFMA kernel ran, 0: the direct one); the MFMA kernel's rows per block, or 0)."""
+    lib = load_library(lib_path)
+    x, w, scale, shift = _f32(x), _f32(w), _f32(scale), _f32(shift)
+    res = None if res is None else _f32(res)
+    fo = (fi - 1) // sf + 1 if fi >= 1 and sf >= 1 else 1
+    assert x.size == n * ci * fi * T and w.size == 32 * ci * ks * ks and scale.size == shift.size == 32
+    assert res is None or res.size == n * 32 * fo * T
+    y = np.full((n, T, 32 * fo) if tdnn_out else (n, 32, fo, T), fill, dtype=np.float32)
+    route, used = C.c_int32(-1), C.c_int32(-1)
+    p = _aux_ptr
+    _aux_check(lib, lib.zasr_selftest_campp_conv2d(
+        ks, ci, fi, sf, T, n, int(relu), int(tdnn_out), int(in_tf), int(use_mfma), int(rb), p(x),
+        p(w), p(scale), p(shift), p(res), p(y), C.byref(route), C.byref(used)))
+    return y, route.value, used.value
+
+
+def selftest_campp_cam_mask(h, w1, b1, w2, b2, seg_len: int, fill: float = -777.25,
+                            lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_campp_cam_mask alone: h [n][T][128] -> mexp [n][T][32]."""
+    lib = load_library(lib_path)
+    h, w1, b1, w2, b2 = (_f32(a) for a in (h, w1, b1, w2, b2))
+    n, T, _ = h.shape
+    assert h.shape[2] == 128 and w1.shape == (64, 128) and b1.shape == (64,) and w2.shape == (32, 64) and b2.shape == (32,)
+    m = np.full((n, T, 32), fill, dtype=np.float32)
+    p = _aux_ptr
+    _aux_check(lib, lib.zasr_selftest_campp_cam_mask(n, T, int(seg_len), p(h), p(w1), p(b1), p(w2),
+                                                     p(b2), p(m)))
+    return m
+
+
+def selftest_campp_stats(x, s, b, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_campp_stats alone: x [N][T][C] -> out [N][2 C]."""
+    lib = load_library(lib_path)
+    x, s, b = _f32(x), _f32(s), _f32(b)
+    N, T, Cc = x.shape
+    assert s.shape == (Cc,) and b.shape == (Cc,)
+    out = np.full((N, 2 * Cc), fill, dtype=np.float32)
+    p = _aux_ptr
+    _aux_check(lib, lib.zasr_selftest_campp_stats(N, T, Cc, p(x), p(s), p(b), p(out)))
+    return out
+
+
+def selftest_campp_cmvn(x, fr_off, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_campp_cmvn alone: returns x [rows][80] after the in-place mean removal."""
+    lib = load_library(lib_path)
+    x, fr_off = _f32(x).copy(), _lens(fr_off)
+    assert x.ndim == 2 and x.shape[1] == 80 and fr_off.size >= 2
+    _aux_check(lib, lib.zasr_selftest_campp_cmvn(fr_off.size - 1, x.shape[0],
+                                                 _aux_ptr(fr_off, C.c_int32), _aux_ptr(x)))
+    return x
+
+
+def selftest_campp_gather(rows, win_row, win_n, wf: int, fill: float = -777.25,
+                          lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_campp_gather alone: rows [nrows][80] -> out [nwin][wf][80]."""
+    lib = load_library(lib_path)
+    rows, win_row, win_n = _f32(rows), _lens(win_row), _lens(win_n)
+    assert rows.ndim == 2 and rows.shape[1] == 80 and win_row.shape == win_n.shape
+    out = np.full((win_row.size, wf, 80), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_campp_gather(win_row.size, int(wf), rows.shape[0], _aux_ptr(rows),
+                                                   _aux_ptr(win_row, C.c_int32),
+                                                   _aux_ptr(win_n, C.c_int32), _aux_ptr(out)))
+    return out
+
+
+def selftest_vad_frames(n_windows: int, audio=None, off=None, win_start=None, lens=None, rows576=None,
+                        fill: float = -777.25, lib_path: Optional[str] = None):
+    """launch_vad_frames alone: returns (frames [n_windows * 4][256], maxabs [files] uint32 or
+    None).  rows576 [n_windows][576]: row mode; else file mode, with `lens` after
+    launch_vad_maxabs on a zeroed table."""
+    lib = load_library(lib_path)
+    frames = np.full((n_windows * 4, 256), fill, dtype=np.float32)
+    i64 = lambda a: _aux_ptr(a, C.c_int64)
+    if rows576 is not None:
+        rows576 = _f32(rows576)
+        assert rows576.shape == (n_windows, 576)
+        _aux_check(lib, lib.zasr_selftest_vad_frames(0, n_windows, 0, None, None, None, None,
+                                                     _aux_ptr(rows576), None, _aux_ptr(frames)))
+        return frames, None
+    audio, off, win_start = _f32(audio), _i64(off), _i64(win_start)
+    lens = None if lens is None else _i64(lens)
+    mx = None if lens is None else np.full(off.size, 0x7e7e7e7e, dtype=np.uint32)
+    assert off.shape == win_start.shape and (lens is None or lens.shape == off.shape)
+    _aux_check(lib, lib.zasr_selftest_vad_frames(off.size, n_windows, audio.size, _aux_ptr(audio),
+                                                 i64(off), i64(win_start), i64(lens), None,
+                                                 _aux_ptr(mx, C.c_uint32), _aux_ptr(frames)))
+    return frames, mx
+
+
+def selftest_vad_mag_im2col(S, bins: int, Kp: int, fill: float = -777.25,
+                            lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_vad_mag_im2col alone: S [windows * 4][ldS] -> A [windows * 4][Kp]."""
+    lib = load_library(lib_path)
+    S = _f32(S)
+    assert S.ndim == 2 and S.shape[0] % 4 == 0
+    A = np.full((S.shape[0], Kp), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_vad_im2col(0, S.shape[0] // 4, 0, int(bins), 0, S.shape[1],
+                                                 int(Kp), _aux_ptr(S), _aux_ptr(A)))
+    return A
+
+
+def selftest_vad_im2col(Y, N: int, T: int, stride: int, fill: float = -777.25,
+                        lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_vad_im2col alone: Y [N * T][C] -> A [N * Tout][3 C]."""
+    lib = load_library(lib_path)
+    Y = _f32(Y)
+    assert Y.ndim == 2 and Y.shape[0] == N * T
+    Cc = Y.shape[1]
+    A = np.full((N * ((T - 1) // stride + 1), 3 * Cc), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_vad_im2col(1, N, T, Cc, int(stride), 0, 0, _aux_ptr(Y),
+                                                 _aux_ptr(A)))
+    return A
+
+
+def selftest_vad_lstm(gx, whh, bhh, wd, bd: float, seg_start, seg_count, seg_warm=None, init=None,
+                      want_s: bool = True, want_e: bool = True, fill: float = -777.25,
+                      lib_path: Optional[str] = None):
+    """launch_vad_lstm alone: returns (probs [windows], s_out, e_out [segments][2][128] or None)."""
+    lib = load_library(lib_path)
+    gx, whh, bhh, wd = _f32(gx), _f32(whh), _f32(bhh), _f32(wd)
+    seg_start, seg_count = _i64(seg_start), _lens(seg_count)
+    seg_warm = None if seg_warm is None else _lens(seg_warm)
+    init = None if init is None else _f32(init)
+    nseg = seg_start.size
+    assert gx.ndim == 2 and gx.shape[1] == 512 and whh.shape == (512, 128) and bhh.shape == (512,) and wd.shape == (128,)
+    assert seg_count.size == nseg and (seg_warm is None or seg_warm.size == nseg)
+    assert init is None or init.shape == (nseg, 2, 128)
+    probs = np.full(gx.shape[0], fill, dtype=np.float32)
+    s_out = np.full((nseg, 2, 128), fill, dtype=np.float32) if want_s else None
+    e_out = np.full((nseg, 2, 128), fill, dtype=np.float32) if want_e else None
+    p = _aux_ptr
+    _aux_check(lib, lib.zasr_selftest_vad_lstm(gx.shape[0], nseg, p(gx), p(whh), p(bhh), p(wd), float(bd),
+                                               p(seg_start, C.c_int64), p(seg_count, C.c_int32),
+                                               p(seg_warm, C.c_int32), p(init), p(probs), p(s_out),
+                                               p(e_out)))
+    return probs, s_out, e_out
+
+
+def selftest_vibert_ln(g, b, eps: float, x=None, ids=None, tt=None, L: int = 0, word=None, pos=None,
+                       type_=None, H: Optional[int] = None, fill: float = -777.25,
+                       lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_vibert_layernorm on x [rows][H] (in place; returned), or, with ids,
+    launch_vibert_embed: ids / tt [rows], L, word [V][H], pos [P][H], type_ [TT][H]."""
+    lib = load_library(lib_path)
+    g, b = _f32(g), _f32(b)
+    H = g.size if H is None else H
+    p = _aux_ptr
+    if ids is None:
+        x = _f32(x).copy()
+        assert x.ndim == 2 and x.shape[1] == H
+        _aux_check(lib, lib.zasr_selftest_vibert_ln(x.shape[0], H, 0, None, None, 0, 0, 0, None, None,
+                                                    None, p(g), p(b), float(eps), p(x)))
+        return x
+    ids, tt, word, pos, type_ = _i64(ids), _i64(tt), _f32(word), _f32(pos), _f32(type_)
+    assert ids.shape == tt.shape and word.shape[1] == pos.shape[1] == type_.shape[1] == H
+    x = np.full((ids.size, H), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_vibert_ln(ids.size, H, int(L), p(ids, C.c_int64), p(tt, C.c_int64),
+                                                word.shape[0], pos.shape[0], type_.shape[0], p(word),
+                                                p(pos), p(type_), p(g), p(b), float(eps), p(x)))
+    return x
+
+
+def selftest_vibert_attn(qkv, mask, B: int, L: int, heads: int, H: int, fill: float = -777.25,
+                         lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_vibert_attention alone: qkv [B L][3 H], mask [B L] -> ctx [B L][H]."""
+    lib = load_library(lib_path)
+    qkv, mask = _f32(qkv), _i64(mask)
+    assert qkv.shape == (B * L, 3 * H) and mask.shape == (B * L,)
+    ctx = np.full((B * L, H), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_vibert_attn(B, L, heads, H, _aux_ptr(qkv),
+                                                  _aux_ptr(mask, C.c_int64), _aux_ptr(ctx)))
+    return ctx
+
+
+def selftest_vibert_gather(x, offsets, L: int, fill: float = -777.25,
+                           lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_vibert_gather alone: x [B L][H], offsets [B][W] -> g [B W][H]."""
+    lib = load_library(lib_path)
+    x, offsets = _f32(x), _i64(offsets)
+    B, W = offsets.shape
+    assert x.ndim == 2 and x.shape[0] == B * L
+    g = np.full((B * W, x.shape[1]), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_vibert_gather(B, int(L), W, x.shape[1], _aux_ptr(x),
+                                                    _aux_ptr(offsets, C.c_int64), _aux_ptr(g)))
+    return g
 
 
 def silence_flags(d_wav_ptr: int, n: int, frame_len: int, threshold: float, d_flags_ptr: int,
