@@ -402,6 +402,51 @@ int zasr_sep_trim(zasr_sep* h);
 int zasr_sep_set_profile(zasr_sep* h, int32_t on);
 int zasr_sep_stage_ms(zasr_sep* h, float* ms4);
 
+/* ---- community-1 speaker embeddings (core/speaker_diarization_pure_ort.py) ------------------
+   The embedding stage of the reference's production diarizer: WeSpeaker fbank, the ResNet34
+   encoder over every 10 s chunk, masked statistics pooling per (chunk, local speaker) and the
+   5120 -> 256 projection (_extract_embeddings :769-879, compute_single_embedding :681-707).
+   model_dir holds config.json + model.safetensors (zasr/resnet34.py).  A chunk's embedding does
+   not depend on the other chunks of the call, on its place among them or on the group size.
+   Invalid arguments return ZASR_ERR_INVALID, missing model files ZASR_ERR_NOT_FOUND. */
+typedef struct zasr_emb zasr_emb;
+int zasr_emb_create(const char* model_dir, int32_t device_id, zasr_emb** out);  /* :417-470 */
+void zasr_emb_destroy(zasr_emb* h);
+int32_t zasr_emb_embedding_dim(const zasr_emb* h);                    /* 256 */
+/* frames of the encoder's output for T fbank frames (:849): three stride-2 stages */
+int32_t zasr_emb_num_feat_frames(const zasr_emb* h, int32_t T);
+/* multiply-adds x 2 of the encoder on one input of T frames, from the model's config */
+double zasr_emb_encoder_flops(const zasr_emb* h, int32_t T);
+/* compute_emb_fbank's rows WITHOUT the CMVN (:271-301) of wav[0, n) followed by `tail` zero
+   samples (:812; 0 for none): rows = 1 + (n + tail - 400) / 160 (0 when shorter than a frame),
+   returned in *rows; out [rows][80] (cap floats). */
+int zasr_emb_fbank(zasr_emb* h, const float* wav, int64_t n, int64_t tail, float* out,
+                   int64_t cap, int64_t* rows);
+/* the encoder session's run (:842-845): feats [n][T][80] -> out [n][2560][T'], channel
+   c * 10 + f, host in / out */
+int zasr_emb_encode(zasr_emb* h, const float* feats, int32_t n, int32_t T, float* out);
+/* _extract_embeddings (:803-872) on the 16 kHz signal d_wav[0, total) already in HBM: the fbank
+   image of the signal and 160000 zeros, per chunk c the 998 rows from starts[c] / 160 with
+   CMVN, the encoder, the pooling under masks_u8 [n_chunks][3][n_seg_frames] (the used mask,
+   chosen on the host) and the projection; out [n_chunks][3][256] (host).  Ordered after
+   `stream` (a hipStream_t, 0 = none); synchronises before it returns. */
+int zasr_emb_chunks_device(zasr_emb* h, const float* d_wav, int64_t total, const int64_t* starts,
+                           int32_t n_chunks, const uint8_t* masks_u8, int32_t n_seg_frames,
+                           float* out, void* stream);
+/* compute_single_embedding (:681-707) of wav[0, n) (host): *ok = 0 and out untouched when the
+   segment has fewer than 9 fbank frames (the reference returns None).  Any length up to 2^20
+   fbank frames (2.9 h; 31 KB of activations per frame); longer returns ZASR_ERR_RUNTIME. */
+int zasr_emb_segment(zasr_emb* h, const float* wav, int64_t n, float* out, int32_t* ok);
+/* chunks (or encode inputs) per launch group: 0 = sized from the free memory (31 MB per 10 s
+   chunk, at most 128), else forced; _last_group is the last call's.  Results do not change. */
+int zasr_emb_set_group(zasr_emb* h, int32_t group);
+int32_t zasr_emb_last_group(const zasr_emb* h);
+int zasr_emb_trim(zasr_emb* h);
+/* stage timing on HIP events (off by default): fbank + windows, stem, layer1, layer2, layer3,
+   layer4, pooling, projection of the last call in ms8[0..7] (tools/emb_bench.py) */
+int zasr_emb_set_profile(zasr_emb* h, int32_t on);
+int zasr_emb_stage_ms(zasr_emb* h, float* ms8);
+
 /* ---- device audio front end --------------------------------------------------------------
    Raw PCM -> the 16 kHz mono float32 HBM signal that zasr_decode_device,
    zasr_vad_probs_device and zasr_campp_windows_device read, and the reference's level
@@ -799,6 +844,19 @@ int zasr_selftest_campp_stats(int32_t N, int32_t T, int32_t C, const float* x, c
 int zasr_selftest_campp_cmvn(int32_t nseq, int32_t rows, const int32_t* fr_off, float* x);
 int zasr_selftest_campp_gather(int32_t nwin, int32_t wf, int32_t nrows, const float* rows,
                                const int32_t* win_row, const int32_t* win_n, float* out);
+/* The community-1 embedding kernels, one launch each on host operands; the output keeps what the
+   caller put there wherever the kernel does not write, with guard bytes before and behind it.
+   emb_conv2d: x [n][Fi][Ti][Ci] (the stem, Ci = 1: [n][Ti][Fi]), w [Co][(r ks + q) Ci + ci],
+   bias [Co], res (nullable) and y [n][Fo][To][Co]; ks 1 | 3, stride 1 | 2, Ci, Co in
+   {32, 64, 128, 256}, or Ci = 1 (ks 3, stride 1, ReLU, no residual); route 0 = the launcher's
+   pick, 1 = 32 channels per block, 2 = 64 (Co >= 64); *n_routes returns how many the layer takes.
+   emb_pool: x [n][F][T][C], mask [n][S][nseg] (null with pop), stats [n S][2 C F]. */
+int zasr_selftest_emb_conv2d(int32_t ks, int32_t stride, int32_t ci, int32_t co, int32_t n,
+                             int32_t fi, int32_t ti, int32_t relu, int32_t route, const float* x,
+                             const float* w, const float* bias, const float* res, float* y,
+                             int32_t* n_routes);
+int zasr_selftest_emb_pool(int32_t n, int32_t F, int32_t T, int32_t C, int32_t S, int32_t nseg,
+                           int32_t pop, const float* x, const uint8_t* mask, float* stats);
 int zasr_selftest_vad_frames(int32_t n_files, int64_t n_windows, int64_t n_samples,
                              const float* audio, const int64_t* off, const int64_t* win_start,
                              const int64_t* len, const float* rows576, uint32_t* maxabs,

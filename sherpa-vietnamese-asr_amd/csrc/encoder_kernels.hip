@@ -55,11 +55,17 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
   return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
-template <bool CAMPP>
+// MODE = FBANK_WESPEAKER: the community-1 embedding front end (core/speaker_diarization_pure_ort.py
+// :271-304): samples x 32768, snip_edges framing, knf's in-frame pre-emphasis (the first sample
+// uses itself, as the main form), floor FLT_EPSILON; samples at or beyond the sequence's length
+// read as 0 (the reference's appended zeros, :812), so fr_off may count frames past the signal;
+// the window table is Hamming and the bank 20 Hz .. Nyquist.
+template <int MODE>
 __global__ __launch_bounds__(64 * kFbWaves) void fbank_kernel(
     const float* __restrict__ wav, const long* __restrict__ wav_off,
     const int* __restrict__ nsamp, const int* __restrict__ fr_off, int nseq, int total_frames,
     FbankTables tabs, float* __restrict__ out) {
+  constexpr bool CAMPP = MODE == FBANK_CAMPP, WESPK = MODE == FBANK_WESPEAKER;
   __shared__ double2 sTw[256];  // exp(-2 pi i u / 512), u < 256
   __shared__ float sWin[400];
   __shared__ int sMeta[240];
@@ -104,6 +110,14 @@ __global__ __launch_bounds__(64 * kFbWaves) void fbank_kernel(
         x[k] = base[(long)f * 160 + (i < 400 ? i : 399)];
       }
       ctx = base[f > 0 ? (long)f * 160 - 1 : 0];
+    } else if constexpr (WESPK) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        const int i = lane + 64 * k;
+        const long s = (long)f * 160 + (i < 400 ? i : 399);
+        x[k] = s < n ? base[s] : 0.f;
+      }
+      ctx = 0.f;
     } else {
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
@@ -126,10 +140,10 @@ __global__ __launch_bounds__(64 * kFbWaves) void fbank_kernel(
 #pragma unroll
     for (int k = 0; k < 7; ++k) xv[k] = xn[k];
     const int f0 = fn;
-    if constexpr (CAMPP) {
+    if constexpr (CAMPP || WESPK) {
 #pragma unroll
       for (int k = 0; k < 7; ++k) xv[k] *= 32768.0f;
-      ctx0 = f0 > 0 ? ctxn * 32768.0f : 0.f;
+      ctx0 = CAMPP && f0 > 0 ? ctxn * 32768.0f : 0.f;
     }
     const int nxt = frame + stride < total_frames ? frame + stride : total_frames - 1;
     gather(nxt, xn, ctxn, fn);
@@ -219,7 +233,14 @@ __global__ __launch_bounds__(64 * kFbWaves) void fbank_kernel(
       acc = fmaf(w3, p3, acc);
     }
     for (; k < ln; ++k) acc = fmaf(sMelW[wo + k], pw[st + k], acc);
-    out[(long)frame * 80 + m] = logf(fmaxf(acc, CAMPP ? 1.0f : 1.1920928955078125e-07f));
+    if constexpr (WESPK) {
+      // the floor's logarithm as the correctly rounded constant (the device logf is 1 ulp off
+      // there): rows of the zero tail are log(FLT_EPSILON) exactly, as knf's are
+      out[(long)frame * 80 + m] =
+          acc > 1.1920928955078125e-07f ? logf(acc) : -0x1.fe2804p+3f;
+    } else {
+      out[(long)frame * 80 + m] = logf(fmaxf(acc, CAMPP ? 1.0f : 1.1920928955078125e-07f));
+    }
   }
   __builtin_amdgcn_wave_barrier();  // the next frame rewrites this wave's A / B images
   }
@@ -227,16 +248,25 @@ __global__ __launch_bounds__(64 * kFbWaves) void fbank_kernel(
 
 void launch_fbank(const float* wav, const long* wav_off, const int* nsamp, const int* fr_off,
                   int nseq, int total_frames, const FbankTables& tabs, float* out,
-                  hipStream_t st, bool campp) {
+                  hipStream_t st, FbankMode mode) {
   if (total_frames <= 0) return;
-  if (campp)
-    ZASR_LAUNCH(fbank_kernel<true>, dim3(std::min(cdiv(total_frames, kFbWaves), kFbBlocks)),
-                       dim3(64 * kFbWaves), 0, st, wav, wav_off, nsamp, fr_off, nseq, total_frames,
-                       tabs, out);
+  const dim3 grid(std::min(cdiv(total_frames, kFbWaves), kFbBlocks)), block(64 * kFbWaves);
+  if (mode == FBANK_CAMPP)
+    ZASR_LAUNCH(fbank_kernel<FBANK_CAMPP>, grid, block, 0, st, wav, wav_off, nsamp, fr_off, nseq,
+                total_frames, tabs, out);
+  else if (mode == FBANK_WESPEAKER)
+    ZASR_LAUNCH(fbank_kernel<FBANK_WESPEAKER>, grid, block, 0, st, wav, wav_off, nsamp, fr_off,
+                nseq, total_frames, tabs, out);
   else
-    ZASR_LAUNCH(fbank_kernel<false>, dim3(std::min(cdiv(total_frames, kFbWaves), kFbBlocks)),
-                       dim3(64 * kFbWaves), 0, st, wav, wav_off, nsamp, fr_off, nseq, total_frames,
-                       tabs, out);
+    ZASR_LAUNCH(fbank_kernel<FBANK_MAIN>, grid, block, 0, st, wav, wav_off, nsamp, fr_off, nseq,
+                total_frames, tabs, out);
+}
+
+void launch_fbank(const float* wav, const long* wav_off, const int* nsamp, const int* fr_off,
+                  int nseq, int total_frames, const FbankTables& tabs, float* out,
+                  hipStream_t st, bool campp) {
+  launch_fbank(wav, wav_off, nsamp, fr_off, nseq, total_frames, tabs, out, st,
+               campp ? FBANK_CAMPP : FBANK_MAIN);
 }
 
 // =====================================================================================

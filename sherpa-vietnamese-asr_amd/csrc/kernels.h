@@ -29,6 +29,13 @@ struct FbankTables {
 void launch_fbank(const float* wav, const long* wav_off, const int* nsamp, const int* fr_off,
                   int nseq, int total_frames, const FbankTables& tabs, float* out,
                   hipStream_t st, bool campp = false);
+// the same kernel by front end; FBANK_WESPEAKER: x 32768, snip_edges, in-frame pre-emphasis,
+// floor FLT_EPSILON, samples at or beyond nsamp read as 0 (tables: Hamming window, the 20 Hz ..
+// Nyquist bank), so a sequence may be given 1 + (nsamp + tail - 400) / 160 frames
+enum FbankMode : int { FBANK_MAIN = 0, FBANK_CAMPP = 1, FBANK_WESPEAKER = 2 };
+void launch_fbank(const float* wav, const long* wav_off, const int* nsamp, const int* fr_off,
+                  int nseq, int total_frames, const FbankTables& tabs, float* out,
+                  hipStream_t st, FbankMode mode);
 
 // the planner's silence detector (core/asr_engine.py:521-554): flags[f] = RMS of samples
 // [f * frame_len, (f + 1) * frame_len) < threshold in numpy's float32 arithmetic, bit for bit;

@@ -20,6 +20,7 @@
 #include "../../include/zasr.h"
 #include "common.h"
 #include "dense_gemm.h"
+#include "emb.h"
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -1627,6 +1628,89 @@ void selftest_vibert_gather(int B, int L, int W, int H, const float* x, const lo
   launch_vibert_gather(dX.p(), dO.p(), B, L, W, H, o.d.as<float>(), nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   o.down(g, "vibert_gather");
+}
+
+
+// ---- the community-1 embedding kernels (emb_kernels.hip) ----
+namespace {
+// an output with guard bytes before and behind it, holding the caller's values where the kernel
+// does not write
+struct GuardedBoth {
+  size_t bytes;
+  DevBuf d;
+  explicit GuardedBoth(const void* init, size_t bytes_) : bytes(bytes_), d(bytes_ + 2 * kAttnGuard) {
+    ZASR_HIP_CHECK(hipMemset(d.p, 0x5a, bytes + 2 * kAttnGuard));
+    if (bytes) ZASR_HIP_CHECK(hipMemcpy(p(), init, bytes, hipMemcpyHostToDevice));
+  }
+  float* p() const { return reinterpret_cast<float*>(d.as<unsigned char>() + kAttnGuard); }
+  void down(void* out, const char* what) const {
+    std::vector<unsigned char> all(bytes + 2 * kAttnGuard);
+    ZASR_HIP_CHECK(hipMemcpy(all.data(), d.p, all.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < kAttnGuard; ++i)
+      ZASR_REQUIRE(all[i] == 0x5a && all[kAttnGuard + bytes + i] == 0x5a,
+                   std::string("selftest ") + what + ": the kernel wrote outside its output");
+    std::memcpy(out, all.data() + kAttnGuard, bytes);
+  }
+};
+}  // namespace
+
+void selftest_emb_conv2d(int ks, int stride, int ci, int co, int n, int fi, int ti, int relu,
+                         int route, const float* x, const float* w, const float* bias,
+                         const float* res, float* y, int* n_routes) {
+  const std::string m = "selftest emb_conv2d: ";
+  auto okc = [](int c) { return c == 32 || c == 64 || c == 128 || c == 256; };
+  const bool stem = ci == 1;
+  ZASR_REQUIRE(okc(co) && (stem || okc(ci)), m + "Ci, Co in {32, 64, 128, 256}, or Ci = 1 (the stem)");
+  ZASR_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), m + "kernel 1 | 3, stride 1 | 2");
+  ZASR_REQUIRE(!stem || (ks == 3 && stride == 1 && relu && !res && route == 0),
+               m + "the stem is 3x3, stride 1, ReLU, no residual, one route");
+  ZASR_REQUIRE(n >= 1 && fi >= 1 && ti >= 1 && n <= 65535 && fi <= 4096 && ti <= (1 << 20), m + "sizes out of range");
+  const int fo = (fi - 1) / stride + 1, to = (ti - 1) / stride + 1;
+  const size_t nx = (size_t)n * fi * ti * ci, nw = (size_t)co * ks * ks * ci, ny = (size_t)n * fo * to * co;
+  ZASR_REQUIRE(nx <= kAuxMax && ny <= kAuxMax, m + "problem too large");
+  const int routes = stem ? 1 : emb_conv2d_routes(co);
+  if (n_routes) *n_routes = routes;
+  ZASR_REQUIRE(route >= 0 && route <= routes, m + "no such route for this layer");
+  DevIn<float> dX(x, nx), dW(w, nw), dB(bias, co), dR(res, res ? ny : 0);
+  GuardedBoth o(y, ny * 4);
+  if (stem) {
+    launch_emb_stem(dX.p(), dW.p(), dB.p(), n, ti, fi, co, o.p(), nullptr);
+  } else {
+    EmbConv2d a{};
+    a.x = dX.p();
+    a.w = dW.p();
+    a.bias = dB.p();
+    a.res = res ? dR.p() : nullptr;
+    a.y = o.p();
+    a.n = n;
+    a.Fi = fi;
+    a.Ti = ti;
+    a.Ci = ci;
+    a.Fo = fo;
+    a.To = to;
+    a.Co = co;
+    a.ks = ks;
+    a.stride = stride;
+    a.relu = relu ? 1 : 0;
+    launch_emb_conv2d(a, route, nullptr);
+  }
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(y, "emb_conv2d");
+}
+
+void selftest_emb_pool(int n, int F, int T, int C, int S, int nseg, int pop, const float* x,
+                       const unsigned char* mask, float* stats) {
+  const std::string m = "selftest emb_pool: ";
+  ZASR_REQUIRE(n >= 1 && F >= 1 && T >= 1 && C >= 1 && S >= 1 && S <= 4 && (pop || T <= 1024) &&
+                   (size_t)n * F * T * C <= kAuxMax && (size_t)n * S * 2 * C * F <= kAuxMax,
+               m + "sizes out of range");
+  ZASR_REQUIRE(pop || (mask && nseg >= 1 && (size_t)n * S * nseg <= kAuxMax), m + "the masked form takes masks");
+  DevIn<float> dX(x, (size_t)n * F * T * C);
+  DevIn<unsigned char> dM(pop ? nullptr : mask, pop ? 0 : (size_t)n * S * nseg);
+  GuardedBoth o(stats, (size_t)n * S * 2 * C * F * 4);
+  launch_emb_pool(dX.p(), pop ? nullptr : dM.p(), n, F, T, C, S, nseg, pop != 0, o.p(), nullptr);
+  ZASR_HIP_CHECK(hipDeviceSynchronize());
+  o.down(stats, "emb_pool");
 }
 
 }  // namespace zasr

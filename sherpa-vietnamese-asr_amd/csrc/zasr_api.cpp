@@ -14,6 +14,7 @@
 #include "common.h"
 #include "diar.h"
 #include "seg.h"
+#include "emb.h"
 #include "sep.h"
 #include "vad.h"
 #include "vibert.h"
@@ -68,6 +69,10 @@ struct zasr_seg {
 
 struct zasr_sep {
   std::unique_ptr<zasr::SepEngine> eng;
+};
+
+struct zasr_emb {
+  std::unique_ptr<zasr::EmbEngine> eng;
 };
 
 struct zasr_audio {
@@ -526,6 +531,144 @@ int zasr_sep_stage_ms(zasr_sep* h, float* ms4) {
   std::lock_guard<std::mutex> lk(h->eng->mu);
   std::memcpy(ms4, h->eng->stage_ms(), sizeof(float) * zasr::SepEngine::kStages);
   return ZASR_OK;
+}
+
+// ---- community-1 speaker embeddings (core/speaker_diarization_pure_ort.py) ----
+int zasr_emb_create(const char* model_dir, int32_t device_id, zasr_emb** out) {  // :417-470
+  if (!model_dir || !out) return fail(ZASR_ERR_INVALID, "null model_dir/out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_emb;
+    try {
+      h->eng.reset(new zasr::EmbEngine(model_dir, device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_emb_destroy(zasr_emb* h) { delete h; }
+
+int32_t zasr_emb_embedding_dim(const zasr_emb* h) { return h ? h->eng->embed_dim() : 0; }
+
+// :849 out[0].shape[1]
+int32_t zasr_emb_num_feat_frames(const zasr_emb* h, int32_t T) {
+  return h ? h->eng->num_feat_frames(T) : 0;
+}
+
+double zasr_emb_encoder_flops(const zasr_emb* h, int32_t T) {
+  return h && T >= 1 ? h->eng->encoder_flops(T) : 0.0;
+}
+
+int zasr_emb_fbank(zasr_emb* h, const float* wav, int64_t n, int64_t tail, float* out, int64_t cap,
+                   int64_t* rows) {  // :271-301, :807-817
+  if (!h || !rows || n < 0 || tail < 0 || (n > 0 && !wav)) return fail(ZASR_ERR_INVALID, "null argument");
+  if (n > INT32_MAX || tail > INT32_MAX) return fail(ZASR_ERR_INVALID, "embedding: signal too long");
+  const int64_t r = zasr::EmbEngine::fbank_rows((long)n, (long)tail);
+  *rows = r;
+  if (r * 80 > cap || (r > 0 && !out)) return fail(ZASR_ERR_INVALID, "output buffer too small");
+  if (r == 0) return ZASR_OK;
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->fbank_host(wav, (long)n, (long)tail, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_emb_encode(zasr_emb* h, const float* feats, int32_t n, int32_t T, float* out) {  // :842-845
+  if (!h || !feats || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (n <= 0 || T <= 0 || T > (1 << 16)) return fail(ZASR_ERR_INVALID, "embedding: n >= 1, 1 <= T <= 65536");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->encode_host(feats, n, T, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_emb_chunks_device(zasr_emb* h, const float* d_wav, int64_t total, const int64_t* starts,
+                           int32_t n_chunks, const uint8_t* masks_u8, int32_t n_seg_frames,
+                           float* out, void* stream) {  // :803-872
+  if (!h || !d_wav || !starts || !masks_u8 || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (n_chunks <= 0 || n_seg_frames <= 0 || total <= 0 || total > INT32_MAX - 160000)
+    return fail(ZASR_ERR_INVALID, "embedding: n_chunks, n_seg_frames, total must be positive");
+  for (int32_t c = 0; c < n_chunks; ++c)
+    if (starts[c] < 0) return fail(ZASR_ERR_INVALID, "embedding: negative chunk start");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->chunks_device(d_wav, (long)total, reinterpret_cast<const long*>(starts), n_chunks,
+                          masks_u8, n_seg_frames, out, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_emb_segment(zasr_emb* h, const float* wav, int64_t n, float* out, int32_t* ok) {  // :681-707
+  if (!h || !out || !ok || n < 0 || (n > 0 && !wav)) return fail(ZASR_ERR_INVALID, "null argument");
+  *ok = 0;
+  if (n > INT32_MAX) return fail(ZASR_ERR_INVALID, "embedding: segment too long");
+  if (zasr::EmbEngine::fbank_rows((long)n, 0) < 9) return ZASR_OK;  // :690 "too short"
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    *ok = h->eng->segment_host(wav, (long)n, out) ? 1 : 0;
+    return (int)ZASR_OK;
+  });
+}
+
+// the reference's embedding_batch_size (:822) bounds the host batch; here the launch group
+int zasr_emb_set_group(zasr_emb* h, int32_t group) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  if (group < 0 || group > zasr::EmbEngine::kMaxGroup)
+    return fail(ZASR_ERR_INVALID, "embedding: group must be 0 (automatic) or 1 .. 128");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_group(group);
+  return ZASR_OK;
+}
+
+int32_t zasr_emb_last_group(const zasr_emb* h) { return h ? h->eng->last_group() : 0; }
+
+int zasr_emb_trim(zasr_emb* h) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->trim();
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_emb_set_profile(zasr_emb* h, int32_t on) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_profile(on != 0);
+  return ZASR_OK;
+}
+
+int zasr_emb_stage_ms(zasr_emb* h, float* ms8) {
+  if (!h || !ms8) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  std::memcpy(ms8, h->eng->stage_ms(), sizeof(float) * zasr::EmbEngine::kStages);
+  return ZASR_OK;
+}
+
+int zasr_selftest_emb_conv2d(int32_t ks, int32_t stride, int32_t ci, int32_t co, int32_t n,
+                             int32_t fi, int32_t ti, int32_t relu, int32_t route, const float* x,
+                             const float* w, const float* bias, const float* res, float* y,
+                             int32_t* n_routes) {
+  if (!x || !w || !bias || !y) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_emb_conv2d(ks, stride, ci, co, n, fi, ti, relu, route, x, w, bias, res, y, n_routes);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_emb_pool(int32_t n, int32_t F, int32_t T, int32_t C, int32_t S, int32_t nseg,
+                           int32_t pop, const float* x, const uint8_t* mask, float* stats) {
+  if (!x || !stats) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_emb_pool(n, F, T, C, S, nseg, pop, x, mask, stats);
+    return (int)ZASR_OK;
+  });
 }
 
 int zasr_campp_fbank(zasr_campp* h, const float* wav, int64_t n, float* out, int64_t cap,

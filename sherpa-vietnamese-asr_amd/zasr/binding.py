@@ -35,6 +35,11 @@ EXPORTS = (
     "zasr_sep_create", "zasr_sep_destroy", "zasr_sep_min_samples", "zasr_sep_separate",
     "zasr_sep_separate_device", "zasr_sep_set_budget", "zasr_sep_last_groups", "zasr_sep_trim",
     "zasr_sep_set_profile", "zasr_sep_stage_ms",
+    "zasr_emb_create", "zasr_emb_destroy", "zasr_emb_embedding_dim", "zasr_emb_num_feat_frames",
+    "zasr_emb_encoder_flops", "zasr_emb_fbank", "zasr_emb_encode", "zasr_emb_chunks_device",
+    "zasr_emb_segment", "zasr_emb_set_group", "zasr_emb_last_group", "zasr_emb_trim",
+    "zasr_emb_set_profile", "zasr_emb_stage_ms",
+    "zasr_selftest_emb_conv2d", "zasr_selftest_emb_pool",
     "zasr_create_stream", "zasr_destroy_stream", "zasr_stream_accept_waveform",
     "zasr_decode_stream", "zasr_decode_streams", "zasr_stream_is_decoded",
     "zasr_stream_num_tokens", "zasr_stream_num_frames", "zasr_stream_tokens",
@@ -261,6 +266,38 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_sep_set_profile.restype = C.c_int
     lib.zasr_sep_stage_ms.argtypes = [P, fp]
     lib.zasr_sep_stage_ms.restype = C.c_int
+    lib.zasr_emb_create.argtypes = [C.c_char_p, I32, C.POINTER(P)]
+    lib.zasr_emb_create.restype = C.c_int
+    lib.zasr_emb_destroy.argtypes = [P]
+    lib.zasr_emb_destroy.restype = None
+    lib.zasr_emb_embedding_dim.argtypes = [P]
+    lib.zasr_emb_embedding_dim.restype = I32
+    lib.zasr_emb_num_feat_frames.argtypes = [P, I32]
+    lib.zasr_emb_num_feat_frames.restype = I32
+    lib.zasr_emb_encoder_flops.argtypes = [P, I32]
+    lib.zasr_emb_encoder_flops.restype = C.c_double
+    lib.zasr_emb_fbank.argtypes = [P, fp, I64, I64, fp, I64, C.POINTER(I64)]
+    lib.zasr_emb_fbank.restype = C.c_int
+    lib.zasr_emb_encode.argtypes = [P, fp, I32, I32, fp]
+    lib.zasr_emb_encode.restype = C.c_int
+    lib.zasr_emb_chunks_device.argtypes = [P, P, I64, C.POINTER(I64), I32, C.POINTER(C.c_uint8), I32, fp, P]
+    lib.zasr_emb_chunks_device.restype = C.c_int
+    lib.zasr_emb_segment.argtypes = [P, fp, I64, fp, C.POINTER(I32)]
+    lib.zasr_emb_segment.restype = C.c_int
+    lib.zasr_emb_set_group.argtypes = [P, I32]
+    lib.zasr_emb_set_group.restype = C.c_int
+    lib.zasr_emb_last_group.argtypes = [P]
+    lib.zasr_emb_last_group.restype = I32
+    lib.zasr_emb_trim.argtypes = [P]
+    lib.zasr_emb_trim.restype = C.c_int
+    lib.zasr_emb_set_profile.argtypes = [P, I32]
+    lib.zasr_emb_set_profile.restype = C.c_int
+    lib.zasr_emb_stage_ms.argtypes = [P, fp]
+    lib.zasr_emb_stage_ms.restype = C.c_int
+    lib.zasr_selftest_emb_conv2d.argtypes = [I32] * 9 + [fp, fp, fp, fp, fp, C.POINTER(I32)]
+    lib.zasr_selftest_emb_conv2d.restype = C.c_int
+    lib.zasr_selftest_emb_pool.argtypes = [I32] * 7 + [fp, C.POINTER(C.c_uint8), fp]
+    lib.zasr_selftest_emb_pool.restype = C.c_int
     lib.zasr_silence_flags.argtypes = [P, I64, I32, C.c_float, P, P]
     lib.zasr_silence_flags.restype = C.c_int
     # offline streams (the sherpa-onnx OfflineStream surface, zasr/offline.py)
@@ -1037,6 +1074,49 @@ def selftest_campp_gather(rows, win_row, win_n, wf: int, fill: float = -777.25,
     _aux_check(lib, lib.zasr_selftest_campp_gather(win_row.size, int(wf), rows.shape[0], _aux_ptr(rows),
                                                    _aux_ptr(win_row, C.c_int32),
                                                    _aux_ptr(win_n, C.c_int32), _aux_ptr(out)))
+    return out
+
+
+def selftest_emb_conv2d(x, w, bias, ks: int, stride: int, res=None, relu: bool = True, route: int = 0,
+                        fill: float = -777.25, lib_path: Optional[str] = None):
+    """launch_emb_conv2d (or, for Ci = 1, launch_emb_stem) alone: x [n][Fi][Ti][Ci] (the stem:
+    [n][Ti][Fi]), w [Co][ks][ks][Ci] (tap-major, ci contiguous), bias [Co], res like the output;
+    returns (y [n][Fo][To][Co], routes the layer takes)."""
+    lib = load_library(lib_path)
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    co = w.shape[0]
+    if x.ndim == 3:
+        n, ti, fi = x.shape
+        ci = 1
+    else:
+        n, fi, ti, ci = x.shape
+    assert w.size == co * ks * ks * ci and bias.shape == (co,)
+    fo, to = (fi - 1) // stride + 1, (ti - 1) // stride + 1
+    y = np.full((n, fo, to, co), fill, dtype=np.float32)
+    res = None if res is None else _f32(res)
+    assert res is None or res.shape == y.shape
+    routes = C.c_int32(0)
+    _aux_check(lib, lib.zasr_selftest_emb_conv2d(int(ks), int(stride), ci, co, n, fi, ti, int(bool(relu)),
+                                                 int(route), _aux_ptr(x), _aux_ptr(w), _aux_ptr(bias),
+                                                 _aux_ptr(res), _aux_ptr(y), C.byref(routes)))
+    return y, int(routes.value)
+
+
+def selftest_emb_pool(x, mask=None, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_emb_pool alone: x [n][F][T][C], mask uint8 [n][S][nseg] (None: the unmasked
+    population form, S = 1) -> stats [n][S][2 C F]."""
+    lib = load_library(lib_path)
+    x = _f32(x)
+    n, F, T, Cc = x.shape
+    if mask is None:
+        S, nseg, m = 1, 0, None
+    else:
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert m.ndim == 3 and m.shape[0] == n
+        S, nseg = m.shape[1], m.shape[2]
+    out = np.full((n, S, 2 * Cc * F), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_emb_pool(n, F, T, Cc, S, nseg, int(m is None), _aux_ptr(x),
+                                               _aux_ptr(m, C.c_uint8), _aux_ptr(out)))
     return out
 
 
@@ -1872,6 +1952,198 @@ class SepSession:
         if x.ndim != 2 or x.shape[0] != 1:
             raise ZasrError("separation session: mixture [1, T]")
         return [self.separate([x[0]])[0][None]]
+
+
+class _EmbValue:
+    """OrtValue-shaped holder: .numpy()."""
+
+    def __init__(self, a: np.ndarray):
+        self._a = a
+
+    def numpy(self) -> np.ndarray:
+        return self._a
+
+
+class _EmbOutput:
+    def __init__(self, name: str):
+        self.name = name
+
+
+class _EmbIoBinding:
+    """The io-binding surface core/speaker_diarization_pure_ort.py:823-845 drives."""
+
+    def __init__(self):
+        self.inputs = {}
+        self.output_names = []
+        self.outputs = []
+
+    def bind_cpu_input(self, name: str, array) -> None:
+        self.inputs[name] = array
+
+    def bind_output(self, name: str, *args, **kwargs) -> None:
+        if name not in self.output_names:
+            self.output_names.append(name)
+
+    def get_outputs(self):
+        return self.outputs
+
+    def clear_binding_inputs(self) -> None:
+        self.inputs = {}
+
+    def clear_binding_outputs(self) -> None:
+        self.output_names, self.outputs = [], []
+
+
+class EmbSession:
+    """Community-1 speaker embeddings on the GPU: the encoder session of
+    core/speaker_diarization_pure_ort.py.  run(None, {"fbank_features": x [n, T, 80]}) ->
+    [frame features [n, 2560, T']], get_outputs(), io_binding() and run_with_iobinding() are
+    the onnxruntime surface the reference drives (:823-845, :699); chunk_embeddings() runs the
+    whole of _extract_embeddings from the 16 kHz signal (host, or already in HBM) and
+    segment_embedding() compute_single_embedding.  A chunk's embedding does not depend on the
+    other chunks of the call."""
+
+    INPUT_NAME = "fbank_features"
+    OUTPUT_NAME = "/resnet/pool/Reshape_output_0"   # convert_onnx/split_pyannote_embedding.py:6
+    STAGES = ("front", "stem", "layer1", "layer2", "layer3", "layer4", "pooling", "projection")
+    CHUNK_FRAMES = 998
+    TAIL = 160000
+    SPEAKERS = 3
+
+    def __init__(self, model_dir: str, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        rc = self.lib.zasr_emb_create(model_dir.encode(), device_id, C.byref(h))
+        if rc != 0:
+            msg = self.lib.zasr_last_error().decode()
+            if rc == 2:
+                raise FileNotFoundError(msg)
+            raise ZasrError(msg)
+        self.handle = h
+        self.model_dir = model_dir
+        self.embedding_dim = int(self.lib.zasr_emb_embedding_dim(self.handle))
+        self.feat_width = 2560   # 256 channels x 10 bins: the engine takes feat_dim 80, m_channels 32
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_emb_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def num_feat_frames(self, T: int) -> int:
+        return int(self.lib.zasr_emb_num_feat_frames(self.handle, int(T)))
+
+    def encoder_flops(self, T: int) -> float:
+        """Multiply-adds x 2 of the encoder on one input of T frames (from the model's config)."""
+        return float(self.lib.zasr_emb_encoder_flops(self.handle, int(T)))
+
+    def set_group(self, group: int) -> None:
+        """Inputs per launch group (1 .. 128; 0 = from the free memory).  Results do not change."""
+        self._check(self.lib.zasr_emb_set_group(self.handle, int(group)))
+
+    @property
+    def last_group(self) -> int:
+        return int(self.lib.zasr_emb_last_group(self.handle))
+
+    def trim(self) -> None:
+        """Free the activation workspace the handle keeps between calls."""
+        self._check(self.lib.zasr_emb_trim(self.handle))
+
+    def set_profile(self, on: bool) -> None:
+        self._check(self.lib.zasr_emb_set_profile(self.handle, int(bool(on))))
+
+    def stage_ms(self) -> dict:
+        """Milliseconds of the last call's stages (after set_profile(True))."""
+        ms = (C.c_float * 8)()
+        self._check(self.lib.zasr_emb_stage_ms(self.handle, ms))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    def fbank(self, audio: np.ndarray, tail: int = 0) -> np.ndarray:
+        """compute_emb_fbank's rows before its CMVN (:271-301) of the samples followed by `tail`
+        zeros: [rows, 80]."""
+        x = np.ascontiguousarray(audio, np.float32).reshape(-1)
+        n = x.shape[0]
+        rows = 1 + (n + tail - 400) // 160 if n + tail >= 400 else 0
+        out = np.empty((rows, 80), np.float32)
+        got = C.c_int64(0)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.zasr_emb_fbank(self.handle, x.ctypes.data_as(fp), n, int(tail),
+                                            out.ctypes.data_as(fp), out.size, C.byref(got)))
+        assert got.value == rows
+        return out
+
+    def encode(self, feats: np.ndarray) -> np.ndarray:
+        """feats [n, T, 80] -> frame features [n, 2560, T'] (channel c * 10 + f)."""
+        x = np.ascontiguousarray(feats, np.float32)
+        if x.ndim != 3 or x.shape[2] != 80 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ZasrError("embedding session: fbank_features [n, T, 80]")
+        n, T, _ = x.shape
+        out = np.empty((n, self.feat_width, self.num_feat_frames(T)), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.zasr_emb_encode(self.handle, x.ctypes.data_as(fp), n, T,
+                                             out.ctypes.data_as(fp)))
+        return out
+
+    def chunk_embeddings_device(self, d_audio: int, total: int, chunk_starts, masks_u8,
+                                stream: int = 0) -> np.ndarray:
+        """Embeddings [n_chunks, 3, 256] of the chunks at chunk_starts of the signal
+        d_audio[0, total) (a device pointer) under masks_u8 [n_chunks, 3, n_seg_frames]."""
+        starts = np.ascontiguousarray(chunk_starts, np.int64).reshape(-1)
+        m = np.ascontiguousarray(masks_u8, np.uint8)
+        if m.ndim != 3 or m.shape[0] != starts.shape[0] or m.shape[1] != self.SPEAKERS:
+            raise ZasrError("embedding session: masks [n_chunks, 3, n_seg_frames]")
+        out = np.empty((starts.shape[0], self.SPEAKERS, self.embedding_dim), np.float32)
+        if starts.shape[0] == 0:
+            return out
+        self._check(self.lib.zasr_emb_chunks_device(
+            self.handle, C.c_void_p(d_audio), int(total), starts.ctypes.data_as(C.POINTER(C.c_int64)),
+            starts.shape[0], m.ctypes.data_as(C.POINTER(C.c_uint8)), m.shape[2],
+            out.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(stream)))
+        return out
+
+    def chunk_embeddings(self, audio: np.ndarray, chunk_starts, masks_u8) -> np.ndarray:
+        """The same from a host signal (uploaded through torch for the call)."""
+        import torch
+        x = torch.from_numpy(np.ascontiguousarray(audio, np.float32).reshape(-1)).cuda()
+        torch.cuda.synchronize()
+        return self.chunk_embeddings_device(x.data_ptr(), x.shape[0], chunk_starts, masks_u8)
+
+    def segment_embedding(self, audio: np.ndarray) -> Optional[np.ndarray]:
+        """compute_single_embedding (:681-707): [256], or None under 9 fbank frames.  Any length
+        up to 2^20 fbank frames (2.9 h)."""
+        x = np.ascontiguousarray(audio, np.float32).reshape(-1)
+        out = np.empty(self.embedding_dim, np.float32)
+        ok = C.c_int32(0)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.zasr_emb_segment(self.handle, x.ctypes.data_as(fp), x.shape[0],
+                                              out.ctypes.data_as(fp), C.byref(ok)))
+        return out if ok.value else None
+
+    # ---- the onnxruntime surface ----
+    def run(self, output_names, feeds):
+        return [self.encode(feeds[self.INPUT_NAME])]
+
+    def get_outputs(self):
+        return [_EmbOutput(self.OUTPUT_NAME)]
+
+    def io_binding(self) -> _EmbIoBinding:
+        return _EmbIoBinding()
+
+    def run_with_iobinding(self, binding: _EmbIoBinding) -> None:
+        if self.INPUT_NAME not in binding.inputs:
+            raise ZasrError("embedding session: bind_cpu_input('fbank_features', ...) first")
+        if not binding.output_names:
+            raise ZasrError("embedding session: bind_output(...) first")
+        binding.outputs = [_EmbValue(self.encode(binding.inputs[self.INPUT_NAME]))]
 
 
 AUDIO_FORMATS = {"float32": 0, "int16": 1}  # include/zasr.h ZASR_AUDIO_F32 / ZASR_AUDIO_I16
