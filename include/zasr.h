@@ -911,6 +911,32 @@ int zasr_diar_spectral_embed(zasr_diar* h, const float* X, int32_t x_on_device, 
    counterpart: a diagnostic read by the tests and tools/diar_bench.py) */
 int zasr_diar_last_stats(zasr_diar* h, int32_t* passes, int64_t* applications);
 
+/* ---- community-1 clustering: centroid-linkage AHC on the device ----
+   core/speaker_diarization_pure_ort.py:918-921 (the linkage + fcluster of _cluster; PLDA, VBx,
+   the assignment and the reconstruction are host code in zasr/vbx.py).  2 <= N <= 16384 rows,
+   1 <= D <= 512, a threshold that is not NaN; anything else is ZASR_ERR_INVALID.  Rows must be
+   finite.  Results are bit-identical from run to run and between the forced routes. */
+typedef struct zasr_clu zasr_clu;
+int zasr_clu_create(int32_t device_id, zasr_clu** out);
+void zasr_clu_destroy(zasr_clu* h);
+/* :918-921: labels [N] (host) = the flat clustering of
+   fcluster(linkage(Xn, "centroid", "euclidean"), threshold, "distance") with
+   Xn = X / (|X|_2 + 1e-10) in float32, X float32 [N][D] on the host or (x_on_device) on the
+   device.  Clusters are numbered from 0 by their lowest member row (the reference's numbering is
+   arbitrary and canonicalised at :640).  Synchronises `stream`. */
+int zasr_clu_ahc(zasr_clu* h, const float* X, int32_t x_on_device, int32_t N, int32_t D,
+                 double threshold, int32_t* labels, void* stream);
+/* merges done and rows rescanned by the handle's last ahc (a diagnostic, no reference
+   counterpart) */
+int zasr_clu_last_stats(zasr_clu* h, int64_t* merges, int64_t* rescans);
+/* HIP-event timing of the stages of the next ahc calls: ms4 = normalise (with the upload),
+   pairwise, nearest neighbours, merge loop */
+int zasr_clu_set_profile(zasr_clu* h, int32_t on);
+int zasr_clu_stage_ms(zasr_clu* h, float* ms4);
+/* test hook: force the merge loop's route on this handle (0 = a workgroup of 1024 threads, the
+   default; 1 = 256 threads); *n_routes (nullable) = the number of routes */
+int zasr_selftest_clu_route(zasr_clu* h, int32_t route, int32_t* n_routes);
+
 /* profiling: per-kernel-class HIP-event timing on the handle's stream.  on = 0 off,
    1 kernel classes, 2 kernel classes with the encoder GEMMs split by shape
    ("enc_gemm|M|K|N|w16|a16|c16|epi" class names, for the per-shape roofline table) */

@@ -11,6 +11,7 @@
 #include "../../include/zasr.h"
 #include "audio.h"
 #include "campp.h"
+#include "clu.h"
 #include "common.h"
 #include "diar.h"
 #include "seg.h"
@@ -82,6 +83,10 @@ struct zasr_audio {
 struct zasr_diar {
   std::unique_ptr<zasr::DiarEngine> eng;
   int last_passes = 0;
+};
+
+struct zasr_clu {
+  std::unique_ptr<zasr::CluEngine> eng;
 };
 
 namespace {
@@ -1628,6 +1633,70 @@ int zasr_diar_last_stats(zasr_diar* h, int32_t* passes, int64_t* applications) {
   std::lock_guard<std::mutex> lk(h->eng->mu);
   if (passes) *passes = h->last_passes;
   if (applications) *applications = h->eng->last_applications;
+  return ZASR_OK;
+}
+
+// ---- community-1 clustering: centroid AHC (:918-921) ----
+int zasr_clu_create(int32_t device_id, zasr_clu** out) {
+  if (!out) return fail(ZASR_ERR_INVALID, "null out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_clu;
+    try {
+      h->eng.reset(new zasr::CluEngine(device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_clu_destroy(zasr_clu* h) { delete h; }
+
+int zasr_clu_ahc(zasr_clu* h, const float* X, int32_t x_on_device, int32_t N, int32_t D,
+                 double threshold, int32_t* labels, void* stream) {  // :918-921
+  if (N < zasr::kCluMinN || N > zasr::kCluMaxN)
+    return fail(ZASR_ERR_INVALID, "N must be in 2..16384 rows");
+  if (D < 1 || D > zasr::kCluMaxD) return fail(ZASR_ERR_INVALID, "D must be in 1..512");
+  if (threshold != threshold) return fail(ZASR_ERR_INVALID, "threshold is NaN");
+  if (!h || !X || !labels) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->ahc(X, x_on_device != 0, N, D, threshold, labels, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_clu_last_stats(zasr_clu* h, int64_t* merges, int64_t* rescans) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  if (merges) *merges = h->eng->last_merges;
+  if (rescans) *rescans = h->eng->last_rescans;
+  return ZASR_OK;
+}
+
+int zasr_clu_set_profile(zasr_clu* h, int32_t on) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_profile(on != 0);
+  return ZASR_OK;
+}
+
+int zasr_clu_stage_ms(zasr_clu* h, float* ms4) {
+  if (!h || !ms4) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  std::memcpy(ms4, h->eng->stage_ms(), sizeof(float) * zasr::kCluStages);
+  return ZASR_OK;
+}
+
+int zasr_selftest_clu_route(zasr_clu* h, int32_t route, int32_t* n_routes) {
+  if (n_routes) *n_routes = zasr::kCluRoutes;
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  if (route < 0 || route >= zasr::kCluRoutes) return fail(ZASR_ERR_INVALID, "unknown route");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_route(route);
   return ZASR_OK;
 }
 

@@ -63,6 +63,8 @@ EXPORTS = (
     "zasr_audio_apply_gain",
     "zasr_diar_create", "zasr_diar_destroy", "zasr_diar_similarity", "zasr_diar_prune",
     "zasr_diar_eigs", "zasr_diar_spectral_embed", "zasr_diar_last_stats",
+    "zasr_clu_create", "zasr_clu_destroy", "zasr_clu_ahc", "zasr_clu_last_stats",
+    "zasr_clu_set_profile", "zasr_clu_stage_ms", "zasr_selftest_clu_route",
 )
 
 
@@ -434,6 +436,20 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_diar_spectral_embed.restype = C.c_int
     lib.zasr_diar_last_stats.argtypes = [P, i32p, i64p]
     lib.zasr_diar_last_stats.restype = C.c_int
+    lib.zasr_clu_create.argtypes = [I32, C.POINTER(P)]
+    lib.zasr_clu_create.restype = C.c_int
+    lib.zasr_clu_destroy.argtypes = [P]
+    lib.zasr_clu_destroy.restype = None
+    lib.zasr_clu_ahc.argtypes = [P, P, I32, I32, I32, DBL, P, P]
+    lib.zasr_clu_ahc.restype = C.c_int
+    lib.zasr_clu_last_stats.argtypes = [P, i64p, i64p]
+    lib.zasr_clu_last_stats.restype = C.c_int
+    lib.zasr_clu_set_profile.argtypes = [P, I32]
+    lib.zasr_clu_set_profile.restype = C.c_int
+    lib.zasr_clu_stage_ms.argtypes = [P, fp]
+    lib.zasr_clu_stage_ms.restype = C.c_int
+    lib.zasr_selftest_clu_route.argtypes = [P, I32, i32p]
+    lib.zasr_selftest_clu_route.restype = C.c_int
     if path is None:
         _lib = lib
     return lib
@@ -2351,3 +2367,82 @@ class Diarizer:
         p, a = C.c_int32(), C.c_int64()
         self._check(self.lib.zasr_diar_last_stats(self.handle, C.byref(p), C.byref(a)))
         return int(p.value), int(a.value)
+
+
+class CluSession:
+    """Centroid-linkage AHC of the community-1 diarizer on the device (include/zasr.h
+    zasr_clu_*): fcluster(linkage(l2norm(X), "centroid"), threshold, "distance") as labels
+    numbered by each cluster's lowest member row.  zasr/vbx.py is the host back end over it."""
+
+    STAGES = ("normalise", "pairwise", "nearest", "merge")
+
+    def __init__(self, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        if self.lib.zasr_clu_create(int(device_id), C.byref(h)) != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+        self.handle = h
+        self.device_id = int(device_id)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_clu_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def ahc_into(self, ptr: int, on_device: bool, N: int, D: int, threshold: float,
+                 labels_ptr: int, stream: int = 0) -> int:
+        """The raw call (the tests hand it a guarded output buffer); returns the status."""
+        return self.lib.zasr_clu_ahc(self.handle, C.c_void_p(ptr), int(bool(on_device)), int(N),
+                                     int(D), float(threshold), C.c_void_p(labels_ptr),
+                                     C.c_void_p(stream))
+
+    def ahc(self, X, threshold: float, N: Optional[int] = None, D: Optional[int] = None,
+            stream: int = 0) -> np.ndarray:
+        """int32 labels [N] of the rows of X: a numpy array [N][D] (host) or a device pointer
+        with N and D."""
+        if isinstance(X, np.ndarray):
+            if X.ndim != 2:
+                raise ValueError("X must be [N][D]")
+            keep = np.ascontiguousarray(X, np.float32)
+            N, D = keep.shape
+            ptr, on_device = keep.ctypes.data, False
+        else:
+            if N is None or D is None:
+                raise ValueError("a device X needs N and D")
+            keep, ptr, on_device = None, int(X), True
+        labels = np.full(max(int(N), 0), -1, np.int32)
+        self._check(self.ahc_into(ptr, on_device, N, D, threshold, labels.ctypes.data, stream))
+        del keep
+        return labels
+
+    def last_stats(self):
+        """(merges, rows rescanned) of the last ahc."""
+        m, r = C.c_int64(), C.c_int64()
+        self._check(self.lib.zasr_clu_last_stats(self.handle, C.byref(m), C.byref(r)))
+        return int(m.value), int(r.value)
+
+    def set_profile(self, on: bool) -> None:
+        self._check(self.lib.zasr_clu_set_profile(self.handle, int(bool(on))))
+
+    def stage_ms(self) -> dict:
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zasr_clu_stage_ms(self.handle, ms))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    def n_routes(self) -> int:
+        n = C.c_int32()
+        self.lib.zasr_selftest_clu_route(None, 0, C.byref(n))
+        return int(n.value)
+
+    def force_route(self, route: int) -> None:
+        self._check(self.lib.zasr_selftest_clu_route(self.handle, int(route), None))

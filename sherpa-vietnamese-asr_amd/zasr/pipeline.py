@@ -22,6 +22,7 @@ START token being the last id as after special_tokens_fix.
 from __future__ import annotations
 
 import hashlib
+import os
 from functools import lru_cache
 from typing import Dict, List, Sequence, Tuple
 
@@ -125,11 +126,14 @@ class FullPipe:
     overlap_regions = None  # set by prepare() when a segmentation session is given
     sep = None              # the separation session (set by __init__; None: no overlap segments)
     separator = None        # its zasr.overlap.OverlapSeparator
+    c1 = None               # diarize="community1": its sessions and PLDA (set by __init__)
+    _c1_result = None       # (the signal it was computed from, community1.process's result)
 
     def __init__(self, rec, recd, emb, vib, vib_vocab: int, beam: int = 1,
                  campp_batch: int = 4096, iterations: int = ITERATIONS, vib_batch: int = 0,
                  tokenizer=None, confidence: float = 0.3, case_confidence: float = 0.0,
-                 shard: bool = False, diarize: bool = False, segmentation=None, separation=None):
+                 shard: bool = False, diarize=False, segmentation=None, separation=None,
+                 embedding=None, plda=None):
         """diarize: cluster each pass's window embeddings into speakers (zasr.diarize: the
         reference's process() from the clustering on, :726-830) and add "speaker_segments"
         (who spoke when: [{"start", "end", "speaker"}]) and "speaker_labels" (one per window)
@@ -152,6 +156,14 @@ class FullPipe:
         pass's dict gains "overlap_segments" (parallel {'speaker', 'speaker_id', 'start',
         'end', 'text', 'raw_words', 'overlap': True} segments).
 
+        diarize="community1" (with segmentation=SegSession, embedding=EmbSession and plda = a
+        model directory or vbx.load_plda's dict): the reference's production diarizer instead
+        (zasr.community1.process, DESIGN §4j: PyanNet chunks every second, ResNet34 embeddings,
+        centroid AHC on the device, VBx, reconstruction) on the signal already in HBM, once per
+        prepare(); every pass's dict gains its "speaker_segments" and "overlap_regions".  The CAM++ windows keep
+        the chunk planner's regions.  ValueError when a session or the PLDA is missing, with
+        shard=True (the stage is not split over ranks) or with a separation session.
+
         shard: strong scaling over the ranks of an initialised torch.distributed group (one
         process per GPU, every rank given the same file): each rank decodes its
         zasr.shard.lpt_partition share of the chunk plan and embeds its share of the speech
@@ -163,6 +175,27 @@ class FullPipe:
         self.rec, self.recd, self.emb, self.vib = rec, recd, emb, vib
         self.vib_vocab, self.beam, self.B, self.iterations = vib_vocab, beam, campp_batch, iterations
         self.shard = bool(shard)
+        self.c1 = None
+        if isinstance(diarize, str):
+            if diarize != "community1":
+                raise ValueError(f"diarize: True, False or \"community1\" (got {diarize!r})")
+            if segmentation is None or embedding is None or plda is None:
+                raise ValueError("diarize=\"community1\" needs segmentation=SegSession, "
+                                 "embedding=EmbSession and plda")
+            if shard:
+                raise ValueError("diarize=\"community1\" is not sharded: use it with shard=False")
+            if separation is not None:
+                raise ValueError("separation works from diarize=True's speakers, not community1's")
+            import torch
+            from zasr import vbx
+            from zasr.binding import CluSession
+            self.c1 = {"seg": segmentation, "emb": embedding,
+                       "clu": CluSession(torch.cuda.current_device()),
+                       "plda": vbx.load_plda(os.fspath(plda))
+                       if isinstance(plda, (str, os.PathLike)) else plda}
+            segmentation, diarize = None, False
+        elif embedding is not None or plda is not None:
+            raise ValueError("embedding and plda belong to diarize=\"community1\"")
         self.seg = segmentation
         self.overlap_regions = None
         self.diar = None
@@ -348,8 +381,22 @@ class FullPipe:
                         out["speaker_segments"], out["speaker_labels"] = self.speakers(embs, win)
                     if self.sep is not None:
                         out["overlap_segments"] = self.separate_overlaps(out["speaker_segments"])
+                    if self.c1 is not None:
+                        spk = self.community1_speakers()
+                        out["speaker_segments"] = [dict(seg) for seg in spk]
+                        out["overlap_regions"] = list(spk.overlap_regions)
                     outs.append(out)
         return outs
+
+    def community1_speakers(self):
+        """community1.process of the prepared signal in HBM.  It depends on the signal alone,
+        not on a pass's decode, so it runs once per prepare() and every pass's dict gets a copy
+        of its segments."""
+        if self._c1_result is None or self._c1_result[0] is not self.d_audio:
+            from zasr import community1
+            self._c1_result = (self.d_audio, community1.process(
+                self.d_audio, self.c1["seg"], self.c1["emb"], self.c1["clu"], self.c1["plda"]))
+        return self._c1_result[1]
 
     def speakers(self, embs: np.ndarray, win: np.ndarray):
         """(segments, labels) of one pass's windows (zasr.diarize.diarize).  One GPU: the
