@@ -875,6 +875,67 @@ int zasr_selftest_vibert_attn(int32_t B, int32_t L, int32_t heads, int32_t H, co
                               const int64_t* mask, float* ctx);
 int zasr_selftest_vibert_gather(int32_t B, int32_t L, int32_t W, int32_t H, const float* x,
                                 const int64_t* offsets, float* g);
+/* The PyanNet segmentation and Conv-TasNet separation kernels other than the GEMMs, alone (test
+   infrastructure; tests/test_gpu_segsep_kernels.py against tests/segsep_reference.py).  As the
+   entries above, except that each runs its one launch function of seg.h / sep.h on a stream of
+   its own.  Outputs are in / out with guard bytes behind them; the in-place seg_norm_act and
+   every separation output (the partial sums included) also have guard bytes in front.
+   float2 (mean, rstd) and double2 (sum, sum of squares) arrays are passed as [.][2].
+   seg_chunk_stats: audio [total], starts [n] >= 0 (samples past `total` are zeros), stats [n][2].
+   seg_front: as above plus stats [n][2] from the caller, w0t [251][80] (tap-major); out
+   [n][F1][80], F1 = ((T - 251) / 10 + 1) / 3 >= 1.
+   seg_pool3: x [n][L][C] -> out [n][Fp][C].  seg_norm_act: x [n][F][C] in place, stats
+   [n][C][2], w / b [C].  max_blocks > 0 caps the grid of these grid-stride launches (0: the
+   engine's).  seg_frame_stats: x [n][F][C] -> stats [n][C][2].
+   seg_lstm: gx [n F][1024], whh [2][512][128], out [n F][256]; `group` sequences per workgroup.
+   seg_head: x [rows][128], w [7][128], b [7] -> logits [rows][7], classes [rows].
+   The separation entries take one call's regions as (sig_off, T) each, F = (T - win) / hop + 1
+   frames, and run the launch group [r0, r0 + ng) of it on the region and tile tables the
+   engine's own builder makes for the groups [0, r0) and [r0, r0 + ng); M = the group's frames,
+   nt = its tiles (of at most 32 frames, none across a region edge), rows in region order.
+   sep_frames: signal [n_signal] -> frames [M][win].  sep_tile_sums: x [M][C] -> partial [nt][2].
+   sep_region_stats: partial [nt][2] -> stats [n_regions][2], written for the group's regions.
+   sep_gln_apply: stats [n_regions][2], gamma / beta [C]; src [M][C] -> dst [M][C], or in_place:
+   dst holds the input, src is ignored.  sep_mid: h [M][C], w [3][C] (tap-major), bias [C] -> y
+   [M][C], partial [nt][2].  sep_prelu: x [rows][ld] in place on columns [col0, col0 + C).
+   sep_overlap_add: dec0 / dec1 [M][win], out_off [n_regions] -> out [n_out], region r's two
+   streams at out[out_off[r] + s T + t]. */
+typedef struct zasr_sep_call {
+  int32_t n_regions;
+  const int64_t* sig_off; /* [n_regions] */
+  const int32_t* T;       /* [n_regions] */
+  int32_t r0, ng, win, hop;
+} zasr_sep_call;
+int zasr_selftest_seg_chunk_stats(int64_t total, int32_t n, int32_t T, const float* audio,
+                                  const int64_t* starts, float* stats);
+int zasr_selftest_seg_front(int64_t total, int32_t n, int32_t T, const float* audio,
+                            const int64_t* starts, const float* stats, float in_w, float in_b,
+                            const float* w0t, float* out);
+int zasr_selftest_seg_pool3(int32_t n, int32_t L, int32_t C, int32_t Fp, int32_t max_blocks,
+                            const float* x, float* out);
+int zasr_selftest_seg_frame_stats(int32_t n, int32_t F, int32_t C, const float* x, float* stats);
+int zasr_selftest_seg_norm_act(int32_t n, int32_t F, int32_t C, int32_t max_blocks,
+                               const float* stats, const float* w, const float* b, float* x);
+int zasr_selftest_seg_lstm(int32_t n, int32_t F, int32_t group, const float* gx, const float* whh,
+                           float* out);
+int zasr_selftest_seg_head(int64_t rows, const float* x, const float* w, const float* b,
+                           float* logits, uint8_t* classes);
+int zasr_selftest_sep_frames(const zasr_sep_call* call, int64_t n_signal, const float* signal,
+                             float* frames);
+int zasr_selftest_sep_tile_sums(const zasr_sep_call* call, int32_t C, const float* x,
+                                double* partial);
+int zasr_selftest_sep_region_stats(const zasr_sep_call* call, int32_t C, const double* partial,
+                                   float* stats);
+int zasr_selftest_sep_gln_apply(const zasr_sep_call* call, int32_t C, int32_t in_place,
+                                const float* stats, const float* gamma, const float* beta,
+                                const float* src, float* dst);
+int zasr_selftest_sep_mid(const zasr_sep_call* call, int32_t C, int32_t dil, float slope,
+                          const float* stats, const float* gamma, const float* beta, const float* w,
+                          const float* bias, const float* h, float* y, double* partial);
+int zasr_selftest_sep_prelu(int64_t rows, int32_t C, int32_t ld, int32_t col0, float slope,
+                            int32_t max_blocks, float* x);
+int zasr_selftest_sep_overlap_add(const zasr_sep_call* call, const int64_t* out_off, int64_t n_out,
+                                  const float* dec0, const float* dec1, float* out);
 
 /* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
    core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the

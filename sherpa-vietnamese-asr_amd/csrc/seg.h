@@ -39,12 +39,15 @@ struct SegFrontArgs {
 };
 void launch_seg_front(const SegFrontArgs& a, int n, hipStream_t st);
 // out[n][p][c] = max(x[n][3p .. 3p + 2][c]),  x [n][L][C], out [n][Fp][C], C % 4 == 0
-void launch_seg_pool3(const float* x, int n, int L, int C, int Fp, float* out, hipStream_t st);
+// (max_blocks > 0 caps the grid of the grid-stride kernels; 0 = one thread per float4 up to 65536
+// blocks, what the engine launches)
+void launch_seg_pool3(const float* x, int n, int L, int C, int Fp, float* out, hipStream_t st,
+                      int max_blocks = 0);
 // InstanceNorm statistics over the F frames of x [n][F][C] (C <= 128): stats[n][c] = (mean, rstd)
 void launch_seg_frame_stats(const float* x, int n, int F, int C, float2* stats, hipStream_t st);
 // x = leaky_relu(((x - mean) * rstd) * w[c] + b[c]) in place
 void launch_seg_norm_act(float* x, int n, int F, int C, const float2* stats, const float* w,
-                         const float* b, hipStream_t st);
+                         const float* b, hipStream_t st, int max_blocks = 0);
 struct SegLstmArgs {
   const float* gx;   // [n * F][1024] x W_ih^T + b_ih + b_hh, forward gates | backward gates
   const float* whh;  // [2][512][128]
@@ -57,6 +60,20 @@ void launch_seg_lstm(const SegLstmArgs& a, int group, hipStream_t st);
 // classifier + log_softmax + argmax (lowest index on ties) of x [rows][128]
 void launch_seg_head(const float* x, long rows, const float* w, const float* b, float* logits,
                      unsigned char* classes, hipStream_t st);
+
+// the kernels above alone, one launch function per entry on host operands (selftest.cpp;
+// include/zasr.h zasr_selftest_seg_*): every output in / out, guarded
+void selftest_seg_chunk_stats(long total, int n, int T, const float* audio, const long* starts,
+                              float* stats);
+void selftest_seg_front(long total, int n, int T, const float* audio, const long* starts,
+                        const float* stats, float in_w, float in_b, const float* w0t, float* out);
+void selftest_seg_pool3(int n, int L, int C, int Fp, int max_blocks, const float* x, float* out);
+void selftest_seg_frame_stats(int n, int F, int C, const float* x, float* stats);
+void selftest_seg_norm_act(int n, int F, int C, int max_blocks, const float* stats, const float* w,
+                           const float* b, float* x);
+void selftest_seg_lstm(int n, int F, int group, const float* gx, const float* whh, float* out);
+void selftest_seg_head(long rows, const float* x, const float* w, const float* b, float* logits,
+                       unsigned char* classes);
 
 class SegEngine {
  public:

@@ -343,14 +343,20 @@ void launch_seg_front(const SegFrontArgs& a, int n, hipStream_t st) {
 }
 
 namespace {
-unsigned stride_grid(long items) { return (unsigned)std::min<long>(cdivl(items, 256), 1 << 16); }
+// blocks of a grid-stride launch over `items` float4s: one thread each up to 65536 blocks, or
+// at most max_blocks when the caller caps it (the kernel-level tests: several passes per thread)
+unsigned stride_grid(long items, int max_blocks) {
+  return (unsigned)std::min<long>(cdivl(items, 256), max_blocks > 0 ? max_blocks : 1 << 16);
+}
 }  // namespace
 
-void launch_seg_pool3(const float* x, int n, int L, int C, int Fp, float* out, hipStream_t st) {
+void launch_seg_pool3(const float* x, int n, int L, int C, int Fp, float* out, hipStream_t st,
+                      int max_blocks) {
   ZASR_REQUIRE(C % 4 == 0 && 3L * Fp <= L, "segmentation: bad pooling geometry");
   const long n4 = (long)n * Fp * (C / 4);
   if (n4 <= 0) return;
-  ZASR_LAUNCH(seg_pool3_kernel, dim3(stride_grid(n4)), dim3(256), 0, st, x, n4, L, C / 4, Fp, out);
+  ZASR_LAUNCH(seg_pool3_kernel, dim3(stride_grid(n4, max_blocks)), dim3(256), 0, st, x, n4, L, C / 4,
+              Fp, out);
 }
 
 void launch_seg_frame_stats(const float* x, int n, int F, int C, float2* stats, hipStream_t st) {
@@ -360,12 +366,12 @@ void launch_seg_frame_stats(const float* x, int n, int F, int C, float2* stats, 
 }
 
 void launch_seg_norm_act(float* x, int n, int F, int C, const float2* stats, const float* w,
-                         const float* b, hipStream_t st) {
+                         const float* b, hipStream_t st, int max_blocks) {
   ZASR_REQUIRE(C % 4 == 0, "segmentation: channels must be a multiple of 4");
   const long n4 = (long)n * F * (C / 4);
   if (n4 <= 0) return;
-  ZASR_LAUNCH(seg_norm_act_kernel, dim3(stride_grid(n4)), dim3(256), 0, st, x, n4, F, C / 4, stats,
-              w, b);
+  ZASR_LAUNCH(seg_norm_act_kernel, dim3(stride_grid(n4, max_blocks)), dim3(256), 0, st, x, n4, F,
+              C / 4, stats, w, b);
 }
 
 void launch_seg_lstm(const SegLstmArgs& a, int group, hipStream_t st) {

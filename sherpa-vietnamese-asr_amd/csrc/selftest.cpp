@@ -9,7 +9,8 @@
 // frame, one greedy window, the final pick) on a caller-supplied search state, and the general
 // GEMMs behind their implicit-im2col and BN-ReLU operand loaders (conv.4 / conv.7 over one
 // z-slice per sequence as a decode launches them; the CAM++ projections of gemm_f32), and the
-// CAM++, Silero VAD and ViBERT kernels, one launch function per entry.
+// CAM++, Silero VAD and ViBERT kernels, one launch function per entry, and the PyanNet and
+// Conv-TasNet kernels likewise (each on a stream of its own).
 // Device 0 of the process, its null stream, synchronous; nothing here is on the decode path.
 #include <algorithm>
 #include <cmath>
@@ -24,6 +25,8 @@
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "seg.h"
+#include "sep.h"
 
 namespace zasr {
 namespace {
@@ -1711,6 +1714,283 @@ void selftest_emb_pool(int n, int F, int T, int C, int S, int nseg, int pop, con
   launch_emb_pool(dX.p(), pop ? nullptr : dM.p(), n, F, T, C, S, nseg, pop != 0, o.p(), nullptr);
   ZASR_HIP_CHECK(hipDeviceSynchronize());
   o.down(stats, "emb_pool");
+}
+
+// ---- the PyanNet and Conv-TasNet kernels (seg_kernels.hip, sep_kernels.hip) ----
+namespace {
+// a stream of the entry's own; made after every buffer, so that the uploads and the guards'
+// fills (null stream) are complete before anything runs on it
+struct FreshStream {
+  hipStream_t s = nullptr;
+  FreshStream() {
+    ZASR_HIP_CHECK(hipDeviceSynchronize());
+    ZASR_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  }
+  ~FreshStream() { (void)hipStreamDestroy(s); }
+  void sync() const { ZASR_HIP_CHECK(hipStreamSynchronize(s)); }
+};
+}  // namespace
+
+void selftest_seg_chunk_stats(long total, int n, int T, const float* audio, const long* starts,
+                              float* stats) {
+  const std::string m = "selftest seg_chunk_stats: ";
+  ZASR_REQUIRE(total >= 1 && (size_t)total <= kAuxMax && n >= 1 && n <= 65535 && T >= 1 && T <= (1 << 24),
+               m + "sizes out of range");
+  for (int k = 0; k < n; ++k) ZASR_REQUIRE(starts[k] >= 0, m + "chunk starts must not be negative");
+  DevIn<float> dA(audio, (size_t)total);
+  DevIn<long> dS(starts, n);
+  GuardedOut o(stats, (size_t)n * 8);
+  FreshStream st;
+  launch_seg_chunk_stats(dA.p(), total, dS.p(), n, T, o.d.as<float2>(), st.s);
+  st.sync();
+  o.down(stats, "seg_chunk_stats");
+}
+
+void selftest_seg_front(long total, int n, int T, const float* audio, const long* starts,
+                        const float* stats, float in_w, float in_b, const float* w0t, float* out) {
+  const std::string m = "selftest seg_front: ";
+  ZASR_REQUIRE(total >= 1 && (size_t)total <= kAuxMax && n >= 1 && n <= (1 << 17) && T >= kSegTaps &&
+                   T <= (1 << 24), m + "sizes out of range");
+  const int F1 = ((T - kSegTaps) / kSegStride0 + 1) / 3;
+  ZASR_REQUIRE(F1 >= 1 && (size_t)n * F1 * kSegC0 <= kAuxMax, m + "T must give at least one pooled frame");
+  for (int k = 0; k < n; ++k) ZASR_REQUIRE(starts[k] >= 0, m + "chunk starts must not be negative");
+  DevIn<float> dA(audio, (size_t)total), dSt(stats, (size_t)n * 2), dW(w0t, (size_t)kSegTaps * kSegC0);
+  DevIn<long> dS(starts, n);
+  GuardedOut o(out, (size_t)n * F1 * kSegC0 * 4);
+  SegFrontArgs a{};
+  a.audio = dA.p();
+  a.total = total;
+  a.starts = dS.p();
+  a.stats = reinterpret_cast<const float2*>(dSt.p());
+  a.in_w = in_w;
+  a.in_b = in_b;
+  a.w0t = dW.p();
+  a.out = o.d.as<float>();
+  a.T = T;
+  a.F1 = F1;
+  FreshStream st;
+  launch_seg_front(a, n, st.s);
+  st.sync();
+  o.down(out, "seg_front");
+}
+
+void selftest_seg_pool3(int n, int L, int C, int Fp, int max_blocks, const float* x, float* out) {
+  ZASR_REQUIRE(n >= 1 && L >= 1 && C >= 1 && Fp >= 1 && max_blocks >= 0 && (size_t)n * L * C <= kAuxMax &&
+                   (size_t)n * Fp * C <= kAuxMax, "selftest seg_pool3: sizes out of range");
+  DevIn<float> dX(x, (size_t)n * L * C);
+  GuardedOut o(out, (size_t)n * Fp * C * 4);
+  FreshStream st;
+  launch_seg_pool3(dX.p(), n, L, C, Fp, o.d.as<float>(), st.s, max_blocks);
+  st.sync();
+  o.down(out, "seg_pool3");
+}
+
+void selftest_seg_frame_stats(int n, int F, int C, const float* x, float* stats) {
+  ZASR_REQUIRE(n >= 1 && n <= 65535 && F >= 1 && C >= 1 && C <= 4096 && (size_t)n * F * C <= kAuxMax,
+               "selftest seg_frame_stats: sizes out of range");
+  DevIn<float> dX(x, (size_t)n * F * C);
+  GuardedOut o(stats, (size_t)n * C * 8);
+  FreshStream st;
+  launch_seg_frame_stats(dX.p(), n, F, C, o.d.as<float2>(), st.s);
+  st.sync();
+  o.down(stats, "seg_frame_stats");
+}
+
+void selftest_seg_norm_act(int n, int F, int C, int max_blocks, const float* stats, const float* w,
+                           const float* b, float* x) {
+  ZASR_REQUIRE(n >= 1 && F >= 1 && C >= 1 && C <= 4096 && max_blocks >= 0 && (size_t)n * F * C <= kAuxMax,
+               "selftest seg_norm_act: sizes out of range");
+  DevIn<float> dS(stats, (size_t)n * C * 2), dW(w, C), dB(b, C);
+  GuardedBoth o(x, (size_t)n * F * C * 4);
+  FreshStream st;
+  launch_seg_norm_act(o.p(), n, F, C, reinterpret_cast<const float2*>(dS.p()), dW.p(), dB.p(), st.s,
+                      max_blocks);
+  st.sync();
+  o.down(x, "seg_norm_act");
+}
+
+void selftest_seg_lstm(int n, int F, int group, const float* gx, const float* whh, float* out) {
+  ZASR_REQUIRE(n >= 1 && n <= 4096 && F >= 1 && F <= 4096 && group >= 1 && group <= 4096,
+               "selftest seg_lstm: sizes out of range");
+  DevIn<float> dG(gx, (size_t)n * F * 8 * kSegH), dW(whh, (size_t)2 * 4 * kSegH * kSegH);
+  GuardedOut o(out, (size_t)n * F * 2 * kSegH * 4);
+  SegLstmArgs a{dG.p(), dW.p(), o.d.as<float>(), n, F};
+  FreshStream st;
+  launch_seg_lstm(a, group, st.s);
+  st.sync();
+  o.down(out, "seg_lstm");
+}
+
+void selftest_seg_head(long rows, const float* x, const float* w, const float* b, float* logits,
+                       unsigned char* classes) {
+  ZASR_REQUIRE(rows >= 1 && rows <= (1 << 20), "selftest seg_head: rows out of range");
+  DevIn<float> dX(x, (size_t)rows * kSegH), dW(w, (size_t)kSegClasses * kSegH), dB(b, kSegClasses);
+  GuardedOut ol(logits, (size_t)rows * kSegClasses * 4), oc(classes, (size_t)rows);
+  FreshStream st;
+  launch_seg_head(dX.p(), rows, dW.p(), dB.p(), ol.d.as<float>(), oc.d.as<unsigned char>(), st.s);
+  st.sync();
+  ol.down(logits, "seg_head (logits)");
+  oc.down(classes, "seg_head (classes)");
+}
+
+namespace {
+// the region and tile tables of one call as the engine's own builder makes them, the launch
+// groups [0, r0) and [r0, r0 + ng) appended in that order
+struct SepTables {
+  std::vector<SepRegion> regions;
+  std::vector<SepTile> tiles;
+  SepGroup g;
+  SepTables(const SepSelftestCall& c, const long* out_off, const std::string& m) {
+    ZASR_REQUIRE(c.n_regions >= 1 && c.n_regions <= (1 << 17) && c.r0 >= 0 && c.ng >= 1 &&
+                     (long)c.r0 + c.ng <= c.n_regions, m + "the group must lie inside the call's regions");
+    ZASR_REQUIRE(c.win >= 1 && c.win <= 4096 && c.hop >= 1 && c.hop <= c.win, m + "win / hop out of range");
+    regions.resize((size_t)c.n_regions);
+    for (int r = 0; r < c.n_regions; ++r) {
+      ZASR_REQUIRE(c.T[r] >= c.win && c.T[r] <= (1 << 24) && c.sig_off[r] >= 0,
+                   m + "every region needs win <= T <= 2^24 and sig_off >= 0");
+      SepRegion& rg = regions[(size_t)r];
+      rg.sig_off = c.sig_off[r];
+      rg.out_off = out_off ? out_off[r] : 0;
+      rg.T = c.T[r];
+      rg.F = (c.T[r] - c.win) / c.hop + 1;
+      rg.row0 = rg.tile0 = 0;
+    }
+    if (c.r0 > 0) sep_fill_group(regions, 0, c.r0, tiles);
+    g = sep_fill_group(regions, c.r0, c.ng, tiles);
+    ZASR_REQUIRE(g.rows >= 1 && g.rows <= (1 << 20), m + "the group's rows out of range");
+  }
+};
+// the tables on the device
+struct SepDevTables {
+  DevIn<SepRegion> regions;
+  DevIn<SepTile> tiles;
+  explicit SepDevTables(const SepTables& t)
+      : regions(t.regions.data(), t.regions.size()), tiles(t.tiles.data(), t.tiles.size()) {}
+};
+}  // namespace
+
+void selftest_sep_frames(const SepSelftestCall& c, long n_signal, const float* signal, float* frames) {
+  const std::string m = "selftest sep_frames: ";
+  const SepTables t(c, nullptr, m);
+  ZASR_REQUIRE(n_signal >= 1 && (size_t)n_signal <= kAuxMax, m + "signal length out of range");
+  for (int r = c.r0; r < c.r0 + c.ng; ++r) {
+    const SepRegion& rg = t.regions[(size_t)r];
+    ZASR_REQUIRE(rg.sig_off + (long)(rg.F - 1) * c.hop + c.win <= n_signal, m + "region outside the signal");
+  }
+  DevIn<float> dS(signal, (size_t)n_signal);
+  const SepDevTables d(t);
+  GuardedBoth o(frames, (size_t)t.g.rows * c.win * 4);
+  FreshStream st;
+  launch_sep_frames(dS.p(), d.regions.p(), d.tiles.p() + t.g.tile0, t.g.n_tiles, c.win, c.hop, o.p(), st.s);
+  st.sync();
+  o.down(frames, "sep_frames");
+}
+
+void selftest_sep_tile_sums(const SepSelftestCall& c, int C, const float* x, double* partial) {
+  const std::string m = "selftest sep_tile_sums: ";
+  const SepTables t(c, nullptr, m);
+  ZASR_REQUIRE(C >= 1 && C <= 4096, m + "C out of range");
+  DevIn<float> dX(x, (size_t)t.g.rows * C);
+  const SepDevTables d(t);
+  GuardedBoth o(partial, (size_t)t.g.n_tiles * 16);
+  FreshStream st;
+  launch_sep_tile_sums(dX.p(), C, d.tiles.p() + t.g.tile0, t.g.n_tiles,
+                       reinterpret_cast<double2*>(o.p()), st.s);
+  st.sync();
+  o.down(partial, "sep_tile_sums");
+}
+
+void selftest_sep_region_stats(const SepSelftestCall& c, int C, const double* partial, float* stats) {
+  const std::string m = "selftest sep_region_stats: ";
+  const SepTables t(c, nullptr, m);
+  ZASR_REQUIRE(C >= 1 && C <= 4096, m + "C out of range");
+  DevIn<double> dP(partial, (size_t)t.g.n_tiles * 2);
+  const SepDevTables d(t);
+  GuardedBoth o(stats, (size_t)c.n_regions * 8);
+  FreshStream st;
+  launch_sep_region_stats(reinterpret_cast<const double2*>(dP.p()), d.regions.p() + c.r0, c.ng, C,
+                          reinterpret_cast<float2*>(o.p()) + c.r0, st.s);
+  st.sync();
+  o.down(stats, "sep_region_stats");
+}
+
+void selftest_sep_gln_apply(const SepSelftestCall& c, int C, int in_place, const float* stats,
+                            const float* gamma, const float* beta, const float* src, float* dst) {
+  const std::string m = "selftest sep_gln_apply: ";
+  const SepTables t(c, nullptr, m);
+  ZASR_REQUIRE(C >= 1 && C <= 4096, m + "C out of range");
+  ZASR_REQUIRE(in_place || src, m + "out of place takes src");
+  const size_t n = (size_t)t.g.rows * C;
+  DevIn<float> dSt(stats, (size_t)c.n_regions * 2), dG(gamma, C), dB(beta, C), dX(in_place ? nullptr : src, in_place ? 0 : n);
+  const SepDevTables d(t);
+  GuardedBoth o(dst, n * 4);
+  FreshStream st;
+  launch_sep_gln_apply(in_place ? o.p() : dX.p(), o.p(), C, d.tiles.p() + t.g.tile0, t.g.n_tiles,
+                       reinterpret_cast<const float2*>(dSt.p()), dG.p(), dB.p(), st.s);
+  st.sync();
+  o.down(dst, "sep_gln_apply");
+}
+
+void selftest_sep_mid(const SepSelftestCall& c, int C, int dil, float slope, const float* stats,
+                      const float* gamma, const float* beta, const float* w, const float* bias,
+                      const float* h, float* y, double* partial) {
+  const std::string m = "selftest sep_mid: ";
+  const SepTables t(c, nullptr, m);
+  ZASR_REQUIRE(C >= 1 && C <= 4096 && dil >= 1 && dil <= (1 << 16), m + "C / dilation out of range");
+  const size_t n = (size_t)t.g.rows * C;
+  DevIn<float> dSt(stats, (size_t)c.n_regions * 2), dG(gamma, C), dB(beta, C), dW(w, (size_t)3 * C),
+      dBi(bias, C), dH(h, n);
+  const SepDevTables d(t);
+  GuardedBoth oy(y, n * 4);
+  GuardedBoth op(partial, (size_t)t.g.n_tiles * 16);
+  SepMidArgs a{};
+  a.h = dH.p();
+  a.y = oy.p();
+  a.stats = reinterpret_cast<const float2*>(dSt.p());
+  a.gamma = dG.p();
+  a.beta = dB.p();
+  a.w = dW.p();
+  a.bias = dBi.p();
+  a.slope = slope;
+  a.C = C;
+  a.dil = dil;
+  a.partial = reinterpret_cast<double2*>(op.p());
+  FreshStream st;
+  launch_sep_mid(a, d.tiles.p() + t.g.tile0, t.g.n_tiles, st.s);
+  st.sync();
+  oy.down(y, "sep_mid");
+  op.down(partial, "sep_mid (partial sums)");
+}
+
+void selftest_sep_prelu(long rows, int C, int ld, int col0, float slope, int max_blocks, float* x) {
+  const std::string m = "selftest sep_prelu: ";
+  ZASR_REQUIRE(rows >= 1 && C >= 1 && ld >= 1 && ld <= (1 << 16) && max_blocks >= 0 &&
+                   (size_t)rows * ld <= kAuxMax, m + "sizes out of range");
+  ZASR_REQUIRE(col0 >= 0 && col0 % 4 == 0 && (long)col0 + C <= ld, m + "columns [col0, col0 + C) must lie inside ld");
+  GuardedBoth o(x, (size_t)rows * ld * 4);
+  FreshStream st;
+  launch_sep_prelu(o.p() + col0, rows, C, ld, slope, st.s, max_blocks);
+  st.sync();
+  o.down(x, "sep_prelu");
+}
+
+void selftest_sep_overlap_add(const SepSelftestCall& c, const long* out_off, long n_out,
+                              const float* dec0, const float* dec1, float* out) {
+  const std::string m = "selftest sep_overlap_add: ";
+  const SepTables t(c, out_off, m);
+  ZASR_REQUIRE(n_out >= 1 && (size_t)n_out <= kAuxMax, m + "output length out of range");
+  for (int r = c.r0; r < c.r0 + c.ng; ++r) {
+    const SepRegion& rg = t.regions[(size_t)r];
+    ZASR_REQUIRE(rg.out_off >= 0 && rg.out_off + 2L * rg.T <= n_out, m + "a region's [2][T] outside the output");
+  }
+  const size_t n = (size_t)t.g.rows * c.win;
+  DevIn<float> d0(dec0, n), d1(dec1, n);
+  const SepDevTables d(t);
+  GuardedBoth o(out, (size_t)n_out * 4);
+  FreshStream st;
+  launch_sep_overlap_add(d0.p(), d1.p(), d.regions.p() + c.r0, c.ng, t.g.max_T, c.win, c.hop, o.p(), st.s);
+  st.sync();
+  o.down(out, "sep_overlap_add");
 }
 
 }  // namespace zasr

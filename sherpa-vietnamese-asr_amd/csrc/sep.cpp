@@ -161,7 +161,7 @@ void SepEngine::collect_marks() {
 }
 
 // One launch group: regions d_regions_[k0, k0 + ng), their tiles d_tiles_[t0, t0 + nt), M rows.
-void SepEngine::run_group(const float* d_signal, const GroupSpan& g, float* d_out) {
+void SepEngine::run_group(const float* d_signal, const SepGroup& g, float* d_out) {
   const long M = g.rows;
   const int nt = g.n_tiles, ng = g.n_regions, os = bn_ + skip_, wide = std::max(hid_, nf_);
   const SepTile* tiles = d_tiles_ + g.tile0;
@@ -232,6 +232,27 @@ void SepEngine::run_group(const float* d_signal, const GroupSpan& g, float* d_ou
   mark(kStDecoder);
 }
 
+SepGroup sep_fill_group(std::vector<SepRegion>& regions, int r0, int ng, std::vector<SepTile>& tiles) {
+  ZASR_REQUIRE(r0 >= 0 && ng >= 0 && (size_t)r0 + (size_t)ng <= regions.size(),
+               "separation: launch group outside the call's regions");
+  SepGroup g{};
+  g.region0 = r0;
+  g.tile0 = (int)tiles.size();
+  for (int r = r0; r < r0 + ng; ++r) {
+    SepRegion& rg = regions[(size_t)r];
+    rg.row0 = (int)g.rows;
+    rg.tile0 = g.n_tiles;
+    for (int f0 = 0; f0 < rg.F; f0 += kSepTile) {
+      tiles.push_back(SepTile{rg.row0 + f0, f0, rg.F, r});
+      ++g.n_tiles;
+    }
+    g.rows += rg.F;
+    g.n_regions += 1;
+    g.max_T = std::max(g.max_T, rg.T);
+  }
+  return g;
+}
+
 void SepEngine::run(const float* d_signal, const std::vector<SepRegion>& in, float* d_out) {
   const size_t n = in.size();
   // events a call that threw left behind must not count into this call's stage times
@@ -239,30 +260,21 @@ void SepEngine::run(const float* d_signal, const std::vector<SepRegion>& in, flo
   marks_.clear();
   h_regions_ = in;
   h_tiles_.clear();
-  std::vector<GroupSpan> groups;
+  std::vector<SepGroup> groups;
   const long per = std::max<long>(1, std::min<long>((long)(budget_ / frame_bytes()), kMaxGroupRows));
-  GroupSpan g{};
-  for (size_t r = 0; r < n; ++r) {
-    SepRegion& rg = h_regions_[r];
-    if (g.n_regions > 0 && (g.rows + rg.F > per || g.n_regions >= kMaxGroupRegions)) {
-      groups.push_back(g);
-      GroupSpan next{};
-      next.region0 = (int)r;
-      next.tile0 = (int)h_tiles_.size();
-      g = next;
+  for (size_t r0 = 0; r0 < n;) {  // a group takes regions while its rows fit (one at least)
+    int ng = 0;
+    long rows = 0;
+    while (r0 + ng < n) {
+      const SepRegion& rg = h_regions_[r0 + ng];
+      ZASR_REQUIRE(rg.F <= kMaxGroupRows, "separation: region too long");
+      if (ng > 0 && (rows + rg.F > per || ng >= kMaxGroupRegions)) break;
+      rows += rg.F;
+      ++ng;
     }
-    ZASR_REQUIRE(rg.F <= kMaxGroupRows, "separation: region too long");
-    rg.row0 = (int)g.rows;
-    rg.tile0 = g.n_tiles;
-    for (int f0 = 0; f0 < rg.F; f0 += kSepTile) {
-      h_tiles_.push_back(SepTile{rg.row0 + f0, f0, rg.F, (int)r});
-      ++g.n_tiles;
-    }
-    g.rows += rg.F;
-    g.n_regions += 1;
-    g.max_T = std::max(g.max_T, rg.T);
+    groups.push_back(sep_fill_group(h_regions_, (int)r0, ng, h_tiles_));
+    r0 += (size_t)ng;
   }
-  if (g.n_regions > 0) groups.push_back(g);
   last_groups_ = (int)groups.size();
   d_regions_ = ws<SepRegion>("regions", n);
   d_tiles_ = ws<SepTile>("tiles", h_tiles_.size());
@@ -271,7 +283,7 @@ void SepEngine::run(const float* d_signal, const std::vector<SepRegion>& in, flo
                                 hipMemcpyHostToDevice, st_));
   ZASR_HIP_CHECK(hipMemcpyAsync(d_tiles_, h_tiles_.data(), h_tiles_.size() * sizeof(SepTile),
                                 hipMemcpyHostToDevice, st_));
-  for (const GroupSpan& gs : groups) run_group(d_signal, gs, d_out);
+  for (const SepGroup& gs : groups) run_group(d_signal, gs, d_out);
   collect_marks();
 }
 

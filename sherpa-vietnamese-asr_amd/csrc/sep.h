@@ -26,7 +26,7 @@ struct SepTile {
   int row0;    // first row of the tile in the ragged [sum F][.] buffers
   int f0;      // its frame within the region
   int F;       // frames of the region
-  int region;  // region of the launch group
+  int region;  // its region, numbered over the whole call (not within the launch group)
 };
 struct SepRegion {
   long sig_off;  // first sample of the region in the signal
@@ -35,6 +35,17 @@ struct SepRegion {
   int row0;      // first row of the region
   int tile0;     // first tile of the region
 };
+
+// a launch group: consecutive regions of a call, their tiles and rows
+struct SepGroup {
+  int region0 = 0, n_regions = 0, tile0 = 0, n_tiles = 0, max_T = 0;
+  long rows = 0;
+};
+// The tables of the launch group regions[r0, r0 + ng) (T and F given): sets every region's row0
+// and tile0, both relative to the group, and appends the group's tiles to `tiles` (a tile's
+// `region` is the index in `regions`, its row0 relative to the group).  The group's tiles start
+// at tiles[tile0]: groups are appended in call order.  sep.cpp.
+SepGroup sep_fill_group(std::vector<SepRegion>& regions, int r0, int ng, std::vector<SepTile>& tiles);
 
 // frames[row][k] = signal[sig_off + 16 f + k], k < 32: the encoder GEMM's A rows
 void launch_sep_frames(const float* signal, const SepRegion* regions, const SepTile* tiles,
@@ -62,13 +73,37 @@ struct SepMidArgs {
   double2* partial;     // [tiles] (sum, sum of squares) of y: the second gLN's statistics
 };
 void launch_sep_mid(const SepMidArgs& a, const SepTile* tiles, int n_tiles, hipStream_t st);
-// x[row][c] = prelu(x[row][c]) for c < C, row stride ld
-void launch_sep_prelu(float* x, long rows, int C, int ld, float slope, hipStream_t st);
-// overlap-add of the decoder GEMMs' [rows][win] frames: out[r][s][t], exact zeros past the
-// last frame's end
+// x[row][c] = prelu(x[row][c]) for c < C, row stride ld (C % 4 == 0, ld % 4 == 0); max_blocks > 0
+// caps the grid-stride launch (0 = one thread per float4 up to 65536 blocks, the engine's)
+void launch_sep_prelu(float* x, long rows, int C, int ld, float slope, hipStream_t st,
+                      int max_blocks = 0);
+// overlap-add of the decoder GEMMs' [rows][win] frames (win = 2 hop, at most 65535 regions):
+// out[r][s][t], exact zeros past the last frame's end
 void launch_sep_overlap_add(const float* dec0, const float* dec1, const SepRegion* regions,
                             int n_regions, int max_T, int win, int hop, float* out,
                             hipStream_t st);
+
+// the kernels above alone, one launch function per entry on host operands (selftest.cpp;
+// include/zasr.h zasr_selftest_sep_*): every output in / out, guarded.  A call's regions are given
+// as (sig_off, T) each, F = (T - win) / hop + 1; the entry runs the launch group [r0, r0 + ng) on
+// the tables sep_fill_group makes for the groups [0, r0) and [r0, r0 + ng).
+struct SepSelftestCall {
+  int n_regions;
+  const long* sig_off;
+  const int* T;
+  int r0, ng, win, hop;
+};
+void selftest_sep_frames(const SepSelftestCall& c, long n_signal, const float* signal, float* frames);
+void selftest_sep_tile_sums(const SepSelftestCall& c, int C, const float* x, double* partial);
+void selftest_sep_region_stats(const SepSelftestCall& c, int C, const double* partial, float* stats);
+void selftest_sep_gln_apply(const SepSelftestCall& c, int C, int in_place, const float* stats,
+                            const float* gamma, const float* beta, const float* src, float* dst);
+void selftest_sep_mid(const SepSelftestCall& c, int C, int dil, float slope, const float* stats,
+                      const float* gamma, const float* beta, const float* w, const float* bias,
+                      const float* h, float* y, double* partial);
+void selftest_sep_prelu(long rows, int C, int ld, int col0, float slope, int max_blocks, float* x);
+void selftest_sep_overlap_add(const SepSelftestCall& c, const long* out_off, long n_out,
+                              const float* dec0, const float* dec1, float* out);
 
 class SepEngine {
  public:
@@ -114,12 +149,8 @@ class SepEngine {
   T* ws(const std::string& name, size_t count) {
     return ws_.get<T>(name, count, &st_);
   }
-  struct GroupSpan {  // a launch group: consecutive regions, their tiles and rows
-    int region0 = 0, n_regions = 0, tile0 = 0, n_tiles = 0, max_T = 0;
-    long rows = 0;
-  };
   void run(const float* d_signal, const std::vector<SepRegion>& regions, float* d_out);
-  void run_group(const float* d_signal, const GroupSpan& g, float* d_out);
+  void run_group(const float* d_signal, const SepGroup& g, float* d_out);
   void mark(int stage);
   void collect_marks();
   size_t frame_bytes() const;

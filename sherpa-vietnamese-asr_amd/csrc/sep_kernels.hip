@@ -80,6 +80,7 @@ __global__ __launch_bounds__(256) void sep_tile_sums_kernel(const float* __restr
 void launch_sep_tile_sums(const float* x, int C, const SepTile* tiles, int n_tiles,
                           double2* partial, hipStream_t st) {
   if (n_tiles <= 0) return;
+  ZASR_REQUIRE(C > 0 && C % 4 == 0, "separation: channels must be a multiple of 4");
   ZASR_LAUNCH(sep_tile_sums_kernel, dim3(n_tiles), dim3(256), 0, st, x, C, tiles, partial);
 }
 
@@ -138,6 +139,7 @@ void launch_sep_gln_apply(const float* src, float* dst, int C, const SepTile* ti
                           const float2* stats, const float* gamma, const float* beta,
                           hipStream_t st) {
   if (n_tiles <= 0) return;
+  ZASR_REQUIRE(C > 0 && C % 4 == 0, "separation: channels must be a multiple of 4");
   ZASR_LAUNCH(sep_gln_apply_kernel, dim3(n_tiles), dim3(256), 0, st, src, dst, C, tiles, stats,
               gamma, beta);
 }
@@ -225,11 +227,13 @@ __global__ void sep_prelu_kernel(float* __restrict__ x, long n4, int C4, int ld,
   }
 }
 
-void launch_sep_prelu(float* x, long rows, int C, int ld, float slope, hipStream_t st) {
+void launch_sep_prelu(float* x, long rows, int C, int ld, float slope, hipStream_t st,
+                      int max_blocks) {
+  ZASR_REQUIRE(C % 4 == 0 && ld % 4 == 0, "separation: PReLU columns and row stride must be multiples of 4");
   const long n4 = rows * (C / 4);
   if (n4 <= 0) return;
-  ZASR_LAUNCH(sep_prelu_kernel, dim3((unsigned)std::min<long>(cdivl(n4, 256), 65536)), dim3(256), 0,
-              st, x, n4, C / 4, ld, slope);
+  const long blocks = std::min<long>(cdivl(n4, 256), max_blocks > 0 ? max_blocks : 65536);
+  ZASR_LAUNCH(sep_prelu_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, n4, C / 4, ld, slope);
 }
 
 // ---- decoder overlap-add (win = 2 hop): a sample sums at most two frame rows ----
@@ -253,6 +257,8 @@ void launch_sep_overlap_add(const float* dec0, const float* dec1, const SepRegio
                             int n_regions, int max_T, int win, int hop, float* out,
                             hipStream_t st) {
   if (n_regions <= 0 || max_T <= 0) return;
+  ZASR_REQUIRE(win == 2 * hop && hop > 0, "separation: the overlap-add needs kernel_size = 2 stride");
+  ZASR_REQUIRE(n_regions <= 65535, "separation: more than 65535 regions in one overlap-add");
   ZASR_LAUNCH(sep_overlap_add_kernel, dim3(cdiv(max_T, 256), n_regions, 2), dim3(256), 0, st, dec0,
               dec1, regions, win, hop, out);
 }

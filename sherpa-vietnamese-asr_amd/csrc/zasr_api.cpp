@@ -1183,6 +1183,148 @@ int zasr_selftest_vibert_gather(int32_t B, int32_t L, int32_t W, int32_t H, cons
   });
 }
 
+// ---- the PyanNet and Conv-TasNet kernels alone ----
+int zasr_selftest_seg_chunk_stats(int64_t total, int32_t n, int32_t T, const float* audio,
+                                  const int64_t* starts, float* stats) {
+  if (!audio || !starts || !stats) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_chunk_stats(total, n, T, audio, reinterpret_cast<const long*>(starts), stats);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_front(int64_t total, int32_t n, int32_t T, const float* audio,
+                            const int64_t* starts, const float* stats, float in_w, float in_b,
+                            const float* w0t, float* out) {
+  if (!audio || !starts || !stats || !w0t || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_front(total, n, T, audio, reinterpret_cast<const long*>(starts), stats, in_w,
+                             in_b, w0t, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_pool3(int32_t n, int32_t L, int32_t C, int32_t Fp, int32_t max_blocks,
+                            const float* x, float* out) {
+  if (!x || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_pool3(n, L, C, Fp, max_blocks, x, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_frame_stats(int32_t n, int32_t F, int32_t C, const float* x, float* stats) {
+  if (!x || !stats) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_frame_stats(n, F, C, x, stats);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_norm_act(int32_t n, int32_t F, int32_t C, int32_t max_blocks,
+                               const float* stats, const float* w, const float* b, float* x) {
+  if (!stats || !w || !b || !x) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_norm_act(n, F, C, max_blocks, stats, w, b, x);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_lstm(int32_t n, int32_t F, int32_t group, const float* gx, const float* whh,
+                           float* out) {
+  if (!gx || !whh || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_lstm(n, F, group, gx, whh, out);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_seg_head(int64_t rows, const float* x, const float* w, const float* b,
+                           float* logits, uint8_t* classes) {
+  if (!x || !w || !b || !logits || !classes) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_seg_head(rows, x, w, b, logits, classes);
+    return (int)ZASR_OK;
+  });
+}
+
+namespace {
+zasr::SepSelftestCall sep_call(const zasr_sep_call* c) {
+  return zasr::SepSelftestCall{c->n_regions, reinterpret_cast<const long*>(c->sig_off), c->T, c->r0,
+                               c->ng, c->win, c->hop};
+}
+bool sep_call_ok(const zasr_sep_call* c) { return c && c->sig_off && c->T; }
+}  // namespace
+
+int zasr_selftest_sep_frames(const zasr_sep_call* call, int64_t n_signal, const float* signal,
+                             float* frames) {
+  if (!sep_call_ok(call) || !signal || !frames) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_frames(sep_call(call), n_signal, signal, frames);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_tile_sums(const zasr_sep_call* call, int32_t C, const float* x,
+                                double* partial) {
+  if (!sep_call_ok(call) || !x || !partial) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_tile_sums(sep_call(call), C, x, partial);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_region_stats(const zasr_sep_call* call, int32_t C, const double* partial,
+                                   float* stats) {
+  if (!sep_call_ok(call) || !partial || !stats) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_region_stats(sep_call(call), C, partial, stats);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_gln_apply(const zasr_sep_call* call, int32_t C, int32_t in_place,
+                                const float* stats, const float* gamma, const float* beta,
+                                const float* src, float* dst) {
+  if (!sep_call_ok(call) || !stats || !gamma || !beta || !dst || (!in_place && !src))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_gln_apply(sep_call(call), C, in_place, stats, gamma, beta, src, dst);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_mid(const zasr_sep_call* call, int32_t C, int32_t dil, float slope,
+                          const float* stats, const float* gamma, const float* beta, const float* w,
+                          const float* bias, const float* h, float* y, double* partial) {
+  if (!sep_call_ok(call) || !stats || !gamma || !beta || !w || !bias || !h || !y || !partial)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_mid(sep_call(call), C, dil, slope, stats, gamma, beta, w, bias, h, y, partial);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_prelu(int64_t rows, int32_t C, int32_t ld, int32_t col0, float slope,
+                            int32_t max_blocks, float* x) {
+  if (!x) return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_prelu(rows, C, ld, col0, slope, max_blocks, x);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_sep_overlap_add(const zasr_sep_call* call, const int64_t* out_off, int64_t n_out,
+                                  const float* dec0, const float* dec1, float* out) {
+  if (!sep_call_ok(call) || !out_off || !dec0 || !dec1 || !out)
+    return fail(ZASR_ERR_INVALID, "null argument");
+  return guarded([&]() {
+    zasr::selftest_sep_overlap_add(sep_call(call), reinterpret_cast<const long*>(out_off), n_out, dec0,
+                                   dec1, out);
+    return (int)ZASR_OK;
+  });
+}
+
 int zasr_selftest_joiner(int32_t mode, int32_t layout, int32_t M, int32_t V, int32_t D,
                          const float* J, const float* W, const float* bias,
                          const int32_t* live_t, const int32_t* live_len, int32_t live_f,

@@ -58,6 +58,11 @@ EXPORTS = (
     "zasr_selftest_campp_cmvn", "zasr_selftest_campp_gather", "zasr_selftest_vad_frames",
     "zasr_selftest_vad_im2col", "zasr_selftest_vad_lstm", "zasr_selftest_vibert_ln",
     "zasr_selftest_vibert_attn", "zasr_selftest_vibert_gather",
+    "zasr_selftest_seg_chunk_stats", "zasr_selftest_seg_front", "zasr_selftest_seg_pool3",
+    "zasr_selftest_seg_frame_stats", "zasr_selftest_seg_norm_act", "zasr_selftest_seg_lstm",
+    "zasr_selftest_seg_head", "zasr_selftest_sep_frames", "zasr_selftest_sep_tile_sums",
+    "zasr_selftest_sep_region_stats", "zasr_selftest_sep_gln_apply", "zasr_selftest_sep_mid",
+    "zasr_selftest_sep_prelu", "zasr_selftest_sep_overlap_add",
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
@@ -112,6 +117,12 @@ class _StTable(C.Structure):
     _fields_ = [("D", C.c_int32), ("jfmt", C.c_int32), ("enc_rows", C.c_int32),
                 ("a", C.c_void_p), ("b", C.c_void_p), ("enc", C.c_void_p),
                 ("enc_off", C.c_void_p), ("J", C.c_void_p), ("j_bytes", C.c_int64)]
+
+
+class _SepCall(C.Structure):  # include/zasr.h zasr_sep_call
+    _fields_ = [("n_regions", C.c_int32), ("sig_off", C.POINTER(C.c_int64)),
+                ("T", C.POINTER(C.c_int32)), ("r0", C.c_int32), ("ng", C.c_int32),
+                ("win", C.c_int32), ("hop", C.c_int32)]
 
 
 _lib = None
@@ -401,6 +412,23 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_selftest_vibert_gather.argtypes = [I32] * 4 + [fp, ip64, fp]
     for _n in ("campp_conv2d", "campp_cam_mask", "campp_stats", "campp_cmvn", "campp_gather",
                "vad_frames", "vad_im2col", "vad_lstm", "vibert_ln", "vibert_attn", "vibert_gather"):
+        getattr(lib, "zasr_selftest_" + _n).restype = C.c_int
+    dp, u8p, cp, fl = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(_SepCall), C.c_float
+    for _n, _a in (("seg_chunk_stats", [I64, I32, I32, fp, ip64, fp]),
+                   ("seg_front", [I64, I32, I32, fp, ip64, fp, fl, fl, fp, fp]),
+                   ("seg_pool3", [I32] * 5 + [fp, fp]),
+                   ("seg_frame_stats", [I32] * 3 + [fp, fp]),
+                   ("seg_norm_act", [I32] * 4 + [fp] * 4),
+                   ("seg_lstm", [I32] * 3 + [fp] * 3),
+                   ("seg_head", [I64, fp, fp, fp, fp, u8p]),
+                   ("sep_frames", [cp, I64, fp, fp]),
+                   ("sep_tile_sums", [cp, I32, fp, dp]),
+                   ("sep_region_stats", [cp, I32, dp, fp]),
+                   ("sep_gln_apply", [cp, I32, I32] + [fp] * 5),
+                   ("sep_mid", [cp, I32, I32, fl] + [fp] * 7 + [dp]),
+                   ("sep_prelu", [I64, I32, I32, I32, fl, I32, fp]),
+                   ("sep_overlap_add", [cp, ip64, I64, fp, fp, fp])):
+        getattr(lib, "zasr_selftest_" + _n).argtypes = _a
         getattr(lib, "zasr_selftest_" + _n).restype = C.c_int
     # device audio front end (zasr/audio.py)
     lib.zasr_audio_create.argtypes = [I32, C.POINTER(P)]
@@ -1256,6 +1284,194 @@ def selftest_vibert_gather(x, offsets, L: int, fill: float = -777.25,
     _aux_check(lib, lib.zasr_selftest_vibert_gather(B, int(L), W, x.shape[1], _aux_ptr(x),
                                                     _aux_ptr(offsets, C.c_int64), _aux_ptr(g)))
     return g
+
+
+# ---- the PyanNet and Conv-TasNet kernels alone (include/zasr.h zasr_selftest_seg_* / _sep_*).
+# Every returned array started as `fill` (or as the given image).
+def selftest_seg_chunk_stats(audio, starts, T: int, fill: float = -777.25,
+                             lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_chunk_stats alone: stats [n][2] = (mean, rstd) of the T samples at starts[k]."""
+    lib = load_library(lib_path)
+    audio, starts = _f32(audio), _i64(starts)
+    stats = np.full((starts.size, 2), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_seg_chunk_stats(audio.size, starts.size, int(T), _aux_ptr(audio),
+                                                      _aux_ptr(starts, C.c_int64), _aux_ptr(stats)))
+    return stats
+
+
+def selftest_seg_front(audio, starts, T: int, stats, in_w: float, in_b: float, w0t,
+                       fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_front alone on the caller's stats [n][2]: out [n][F1][80]."""
+    lib = load_library(lib_path)
+    audio, starts, stats, w0t = _f32(audio), _i64(starts), _f32(stats), _f32(w0t)
+    n = starts.size
+    assert stats.shape == (n, 2) and w0t.shape == (251, 80)
+    F1 = max(((int(T) - 251) // 10 + 1) // 3, 0)
+    out = np.full((n, F1, 80), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_seg_front(audio.size, n, int(T), _aux_ptr(audio),
+                                                _aux_ptr(starts, C.c_int64), _aux_ptr(stats), float(in_w),
+                                                float(in_b), _aux_ptr(w0t), _aux_ptr(out)))
+    return out
+
+
+def selftest_seg_pool3(x, Fp: int, max_blocks: int = 0, fill: float = -777.25,
+                       lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_pool3 alone: x [n][L][C] -> out [n][Fp][C]."""
+    lib = load_library(lib_path)
+    x = _f32(x)
+    n, L, Cc = x.shape
+    out = np.full((n, int(Fp), Cc), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_seg_pool3(n, L, Cc, int(Fp), int(max_blocks), _aux_ptr(x), _aux_ptr(out)))
+    return out
+
+
+def selftest_seg_frame_stats(x, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_frame_stats alone: x [n][F][C] -> stats [n][C][2]."""
+    lib = load_library(lib_path)
+    x = _f32(x)
+    n, F, Cc = x.shape
+    stats = np.full((n, Cc, 2), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_seg_frame_stats(n, F, Cc, _aux_ptr(x), _aux_ptr(stats)))
+    return stats
+
+
+def selftest_seg_norm_act(x, stats, w, b, max_blocks: int = 0, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_norm_act alone: returns x [n][F][C] after the in-place normalise + leaky_relu."""
+    lib = load_library(lib_path)
+    x, stats, w, b = _f32(x).copy(), _f32(stats), _f32(w), _f32(b)
+    n, F, Cc = x.shape
+    assert stats.shape == (n, Cc, 2) and w.shape == (Cc,) and b.shape == (Cc,)
+    _aux_check(lib, lib.zasr_selftest_seg_norm_act(n, F, Cc, int(max_blocks), _aux_ptr(stats), _aux_ptr(w),
+                                                   _aux_ptr(b), _aux_ptr(x)))
+    return x
+
+
+def selftest_seg_lstm(gx, whh, group: int, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_seg_lstm alone: gx [n][F][1024], whh [2][512][128] -> out [n][F][256]."""
+    lib = load_library(lib_path)
+    gx, whh = _f32(gx), _f32(whh)
+    n, F, _ = gx.shape
+    assert gx.shape[2] == 1024 and whh.shape == (2, 512, 128)
+    out = np.full((n, F, 256), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_seg_lstm(n, F, int(group), _aux_ptr(gx), _aux_ptr(whh), _aux_ptr(out)))
+    return out
+
+
+def selftest_seg_head(x, w, b, fill: float = -777.25, lib_path: Optional[str] = None):
+    """launch_seg_head alone: x [rows][128] -> (logits [rows][7], classes uint8 [rows], which
+    start as 255)."""
+    lib = load_library(lib_path)
+    x, w, b = _f32(x), _f32(w), _f32(b)
+    assert x.ndim == 2 and x.shape[1] == 128 and w.shape == (7, 128) and b.shape == (7,)
+    logits = np.full((x.shape[0], 7), fill, dtype=np.float32)
+    classes = np.full(x.shape[0], 255, dtype=np.uint8)
+    _aux_check(lib, lib.zasr_selftest_seg_head(x.shape[0], _aux_ptr(x), _aux_ptr(w), _aux_ptr(b),
+                                               _aux_ptr(logits), _aux_ptr(classes, C.c_uint8)))
+    return logits, classes
+
+
+class SepCall:
+    """One separation call's regions (sig_off, T each) and the launch group [r0, r0 + ng) of it
+    that an entry runs: F frames per region, M rows and nt tiles of the group."""
+
+    def __init__(self, sig_off, T, r0: int, ng: int, win: int = 32, hop: int = 16):
+        self.sig_off, self.T = _i64(sig_off), _lens(T)
+        assert self.sig_off.shape == self.T.shape
+        self.r0, self.ng, self.win, self.hop = int(r0), int(ng), int(win), int(hop)
+        self.F = (self.T.astype(np.int64) - self.win) // self.hop + 1
+        Fg = self.F[self.r0:self.r0 + self.ng]
+        self.M, self.nt = int(Fg.sum()), int(((Fg + 31) // 32).sum())
+        self.c = _SepCall(self.T.size, _aux_ptr(self.sig_off, C.c_int64), _aux_ptr(self.T, C.c_int32),
+                          self.r0, self.ng, self.win, self.hop)
+
+    def ref(self):
+        return C.byref(self.c)
+
+
+def selftest_sep_frames(call: SepCall, signal, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_frames alone: frames [M][win]."""
+    lib = load_library(lib_path)
+    signal = _f32(signal)
+    frames = np.full((call.M, call.win), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_sep_frames(call.ref(), signal.size, _aux_ptr(signal), _aux_ptr(frames)))
+    return frames
+
+
+def selftest_sep_tile_sums(call: SepCall, x, fill: float = -777.25, lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_tile_sums alone: x [M][C] -> partial float64 [nt][2]."""
+    lib = load_library(lib_path)
+    x = _f32(x)
+    assert x.ndim == 2 and x.shape[0] == call.M
+    partial = np.full((call.nt, 2), fill, dtype=np.float64)
+    _aux_check(lib, lib.zasr_selftest_sep_tile_sums(call.ref(), x.shape[1], _aux_ptr(x),
+                                                    _aux_ptr(partial, C.c_double)))
+    return partial
+
+
+def selftest_sep_region_stats(call: SepCall, partial, Cc: int, fill: float = -777.25,
+                              lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_region_stats alone: partial [nt][2] -> stats [n_regions][2] (the group's rows
+    written)."""
+    lib = load_library(lib_path)
+    partial = np.ascontiguousarray(partial, dtype=np.float64)
+    assert partial.shape == (call.nt, 2)
+    stats = np.full((call.T.size, 2), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_sep_region_stats(call.ref(), int(Cc), _aux_ptr(partial, C.c_double),
+                                                       _aux_ptr(stats)))
+    return stats
+
+
+def selftest_sep_gln_apply(call: SepCall, x, stats, gamma, beta, in_place: bool, fill: float = -777.25,
+                           lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_gln_apply alone on x [M][C], out of place or in place: returns the result."""
+    lib = load_library(lib_path)
+    x, stats, gamma, beta = _f32(x), _f32(stats), _f32(gamma), _f32(beta)
+    Cc = x.shape[1]
+    assert x.shape[0] == call.M and stats.shape == (call.T.size, 2) and gamma.shape == beta.shape == (Cc,)
+    dst = x.copy() if in_place else np.full(x.shape, fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_sep_gln_apply(call.ref(), Cc, int(bool(in_place)), _aux_ptr(stats),
+                                                    _aux_ptr(gamma), _aux_ptr(beta),
+                                                    None if in_place else _aux_ptr(x), _aux_ptr(dst)))
+    return dst
+
+
+def selftest_sep_mid(call: SepCall, h, stats, gamma, beta, w, bias, slope: float, dil: int,
+                     fill: float = -777.25, lib_path: Optional[str] = None):
+    """launch_sep_mid alone: h [M][C], w [3][C] -> (y [M][C], partial float64 [nt][2])."""
+    lib = load_library(lib_path)
+    h, stats, gamma, beta, w, bias = (_f32(a) for a in (h, stats, gamma, beta, w, bias))
+    Cc = h.shape[1]
+    assert h.shape[0] == call.M and stats.shape == (call.T.size, 2) and w.shape == (3, Cc)
+    assert gamma.shape == beta.shape == bias.shape == (Cc,)
+    y = np.full(h.shape, fill, dtype=np.float32)
+    partial = np.full((call.nt, 2), fill, dtype=np.float64)
+    p = _aux_ptr
+    _aux_check(lib, lib.zasr_selftest_sep_mid(call.ref(), Cc, int(dil), float(slope), p(stats), p(gamma), p(beta),
+                                              p(w), p(bias), p(h), p(y), p(partial, C.c_double)))
+    return y, partial
+
+
+def selftest_sep_prelu(x, Cc: int, col0: int, slope: float, max_blocks: int = 0,
+                       lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_prelu alone, in place on columns [col0, col0 + C) of x [rows][ld]."""
+    lib = load_library(lib_path)
+    x = _f32(x).copy()
+    rows, ld = x.shape
+    _aux_check(lib, lib.zasr_selftest_sep_prelu(rows, int(Cc), ld, int(col0), float(slope), int(max_blocks),
+                                                _aux_ptr(x)))
+    return x
+
+
+def selftest_sep_overlap_add(call: SepCall, dec0, dec1, out_off, n_out: int, fill: float = -777.25,
+                             lib_path: Optional[str] = None) -> np.ndarray:
+    """launch_sep_overlap_add alone: dec0 / dec1 [M][win] -> out [n_out]."""
+    lib = load_library(lib_path)
+    dec0, dec1, out_off = _f32(dec0), _f32(dec1), _i64(out_off)
+    assert dec0.shape == dec1.shape == (call.M, call.win) and out_off.shape == call.T.shape
+    out = np.full(int(n_out), fill, dtype=np.float32)
+    _aux_check(lib, lib.zasr_selftest_sep_overlap_add(call.ref(), _aux_ptr(out_off, C.c_int64), int(n_out),
+                                                      _aux_ptr(dec0), _aux_ptr(dec1), _aux_ptr(out)))
+    return out
 
 
 def silence_flags(d_wav_ptr: int, n: int, frame_len: int, threshold: float, d_flags_ptr: int,
