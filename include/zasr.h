@@ -38,6 +38,8 @@
  *   zasr_audio_segment_sumsq, zasr_audio_apply_gain
  *                          per_segment_rms_normalize, core/audio_preprocessing.py:46-140 (the
  *                          gain plan itself stays host logic, zasr/audio.py)
+ *   zasr_wpe_run_device    apply_wpe_dereverberation, core/audio_preprocessing.py:157-216, all
+ *                          chunks of a file in one call (per frequency bin)
  */
 #ifndef ZASR_H_
 #define ZASR_H_
@@ -506,6 +508,44 @@ int zasr_audio_apply_gain(zasr_audio* h, float* d_wav, int64_t n, const int64_t*
                           const int64_t* piece_ramp, int32_t n_pieces, const float* ramp_values,
                           int64_t n_ramp_values, float* peak, void* stream);
 
+/* ---- WPE dereverberation -----------------------------------------------------------------
+   apply_wpe_dereverberation (core/audio_preprocessing.py:157-216) for a ragged batch of chunks
+   of one 16 kHz signal: Blackman STFT (512 / 128, 384 zeros of fading at both ends), the
+   weighted prediction error filter of each frequency bin on its own (taps K, delay, iterations;
+   correlation sums and the Cholesky solve in float64), the biorthogonal inverse STFT.  The
+   per-frequency algorithm the function documents, as DESIGN.md 4k defines it; the reference's
+   own call stacks the bins as channels and is not reproduced.  A chunk's result depends on
+   that chunk alone (bit-identical whatever shares the call); a chunk under 1024 samples comes
+   back unchanged (:188-189); a chunk over 60 s is refused. */
+typedef struct zasr_wpe zasr_wpe;
+int zasr_wpe_create(int32_t device_id, zasr_wpe** out);      /* core/audio_preprocessing.py:157-216 */
+void zasr_wpe_destroy(zasr_wpe* h);
+/* Host-only.  STFT frames of a chunk of n samples (core/audio_preprocessing.py:195, nara-wpe's
+   stft with fading): ceil((n + 256) / 128) + 1; -1 for n outside 0..960000. */
+int64_t zasr_wpe_frames(int64_t n);
+/* Chunks [offsets[c], offsets[c] + lens[c]) (host arrays; chunks may overlap) of the device
+   signal d_audio[0, total) -> d_out + out_offsets[c] (device, lens[c] samples each).  taps and
+   delay in 1..16, iterations in 1..8.  Ordered after `stream`'s work; synchronises before
+   returning.  core/audio_preprocessing.py:157-216, once per chunk there. */
+int zasr_wpe_run_device(zasr_wpe* h, const float* d_audio, int64_t total, const int64_t* offsets,
+                        const int64_t* lens, int32_t count, int32_t taps, int32_t delay,
+                        int32_t iterations, float* d_out, const int64_t* out_offsets, void* stream);
+/* The same with audio and out in host memory (core/audio_preprocessing.py:157-216). */
+int zasr_wpe_run(zasr_wpe* h, const float* audio, int64_t total, const int64_t* offsets,
+                 const int64_t* lens, int32_t count, int32_t taps, int32_t delay,
+                 int32_t iterations, float* out, const int64_t* out_offsets);
+/* No counterpart in core/audio_preprocessing.py:157-216 (one chunk per call there): the spectrum
+   bytes the chunks of one launch group may take together (about 7.7 MB per 30 s chunk; a chunk
+   beyond the budget runs alone), the groups of the last call, and the release of the
+   workspace between files.  Results do not depend on the grouping. */
+int zasr_wpe_set_budget(zasr_wpe* h, int64_t bytes);
+int32_t zasr_wpe_last_groups(const zasr_wpe* h);
+int zasr_wpe_trim(zasr_wpe* h);
+/* stage timing on HIP events (off by default): STFT, iterations, inverse STFT of the last call
+   in ms3[0..2] (tools/wpe_bench.py) */
+int zasr_wpe_set_profile(zasr_wpe* h, int32_t on);
+int zasr_wpe_stage_ms(zasr_wpe* h, float* ms3);
+
 /* model facts */
 int32_t zasr_vocab_size(const zasr_recognizer* h);
 int32_t zasr_joiner_dim(const zasr_recognizer* h);
@@ -936,6 +976,18 @@ int zasr_selftest_sep_prelu(int64_t rows, int32_t C, int32_t ld, int32_t col0, f
                             int32_t max_blocks, float* x);
 int zasr_selftest_sep_overlap_add(const zasr_sep_call* call, const int64_t* out_off, int64_t n_out,
                                   const float* dec0, const float* dec1, float* out);
+/* The WPE kernels alone on one chunk, host operands, complex values as (re, im) pairs
+   (core/audio_preprocessing.py:157-216).  wpe_stft: signal [n] -> Y [257][T]
+   complex64, T = zasr_wpe_frames(n), and *max_sq = max |Y|^2.  wpe_iter: one iteration on
+   Y [257][T] with the chunk maximum max_sq (epsilon = 1e-10 max_sq): x from g_prev [257][taps]
+   complex128 (NULL: x = y) -> g [257][taps] complex128, and when given X [T][257] complex64 =
+   y - g^H ytilde and *next_max_sq = max |X|^2.  wpe_istft: X [T][257] -> out [n],
+   T = zasr_wpe_frames(n). */
+int zasr_selftest_wpe_stft(zasr_wpe* h, const float* signal, int64_t n, float* Y, float* max_sq);
+int zasr_selftest_wpe_iter(zasr_wpe* h, const float* Y, int32_t T, int32_t taps, int32_t delay,
+                           float max_sq, const double* g_prev, double* g, float* X,
+                           float* next_max_sq);
+int zasr_selftest_wpe_istft(zasr_wpe* h, const float* X, int32_t T, int64_t n, float* out);
 
 /* ---- speaker diarization: the spectral embedding of Senko's SpectralCluster on the device ----
    core/speaker_diarization_senko_campp_optimized.py:192-228 (_senko_spectral up to the

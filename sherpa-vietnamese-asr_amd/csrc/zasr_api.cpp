@@ -19,6 +19,7 @@
 #include "sep.h"
 #include "vad.h"
 #include "vibert.h"
+#include "wpe.h"
 #include "engine.h"
 #include "host_io.h"
 #include "onnx_io.h"
@@ -78,6 +79,10 @@ struct zasr_emb {
 
 struct zasr_audio {
   std::unique_ptr<zasr::AudioFrontEnd> eng;
+};
+
+struct zasr_wpe {
+  std::unique_ptr<zasr::WpeEngine> eng;
 };
 
 struct zasr_diar {
@@ -1676,6 +1681,155 @@ int zasr_audio_apply_gain(zasr_audio* h, float* d_wav, int64_t n, const int64_t*
                                reinterpret_cast<const long*>(piece_end), piece_gain,
                                reinterpret_cast<const long*>(piece_ramp), n_pieces, ramp_values,
                                (long)n_ramp_values, reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+// ---- WPE dereverberation (wpe.h; core/audio_preprocessing.py:157-216) ----
+namespace {
+int wpe_args_error(int64_t total, const int64_t* offsets, const int64_t* lens, int32_t count,
+                   int32_t taps, int32_t delay, int32_t iterations, const int64_t* out_offsets) {
+  if (count < 0 || total < 0 || (count > 0 && (!offsets || !lens || !out_offsets)))
+    return fail(ZASR_ERR_INVALID, "null argument");
+  if (taps < 1 || taps > zasr::kWpeMaxTaps) return fail(ZASR_ERR_INVALID, "WPE: taps must be in 1..16");
+  if (delay < 1 || delay > zasr::kWpeMaxDelay)
+    return fail(ZASR_ERR_INVALID, "WPE: delay must be in 1..16");
+  if (iterations < 1 || iterations > zasr::kWpeMaxIters)
+    return fail(ZASR_ERR_INVALID, "WPE: iterations must be in 1..8");
+  for (int32_t c = 0; c < count; ++c) {
+    if (lens[c] < 0 || offsets[c] < 0 || lens[c] > total || offsets[c] > total - lens[c])
+      return fail(ZASR_ERR_INVALID, "WPE: chunk outside the signal");
+    if (lens[c] > zasr::kWpeMaxSamples)
+      return fail(ZASR_ERR_INVALID, "WPE: a chunk is at most 60 s (960000 samples)");
+    if (out_offsets[c] < 0) return fail(ZASR_ERR_INVALID, "WPE: negative output offset");
+  }
+  return ZASR_OK;
+}
+}  // namespace
+
+int zasr_wpe_create(int32_t device_id, zasr_wpe** out) {
+  if (!out) return fail(ZASR_ERR_INVALID, "null out");
+  *out = nullptr;
+  return guarded([&]() {
+    auto* h = new zasr_wpe;
+    try {
+      h->eng.reset(new zasr::WpeEngine(device_id));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return (int)ZASR_OK;
+  });
+}
+
+void zasr_wpe_destroy(zasr_wpe* h) { delete h; }
+
+int64_t zasr_wpe_frames(int64_t n) {  // :195, nara-wpe's stft with fading
+  if (n < 0 || n > zasr::kWpeMaxSamples) {
+    fail(ZASR_ERR_INVALID, "WPE: n must be in 0..960000");
+    return -1;
+  }
+  return zasr::wpe_frames((long)n);
+}
+
+int zasr_wpe_run_device(zasr_wpe* h, const float* d_audio, int64_t total, const int64_t* offsets,
+                        const int64_t* lens, int32_t count, int32_t taps, int32_t delay,
+                        int32_t iterations, float* d_out, const int64_t* out_offsets, void* stream) {
+  if (!h || (count > 0 && (!d_audio || !d_out))) return fail(ZASR_ERR_INVALID, "null argument");
+  if (const int rc = wpe_args_error(total, offsets, lens, count, taps, delay, iterations, out_offsets))
+    return rc;
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->run_device(d_audio, (long)total, reinterpret_cast<const long*>(offsets),
+                       reinterpret_cast<const long*>(lens), count, taps, delay, iterations, d_out,
+                       reinterpret_cast<const long*>(out_offsets),
+                       reinterpret_cast<hipStream_t>(stream));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_wpe_run(zasr_wpe* h, const float* audio, int64_t total, const int64_t* offsets,
+                 const int64_t* lens, int32_t count, int32_t taps, int32_t delay,
+                 int32_t iterations, float* out, const int64_t* out_offsets) {
+  if (!h || (count > 0 && (!audio || !out))) return fail(ZASR_ERR_INVALID, "null argument");
+  if (const int rc = wpe_args_error(total, offsets, lens, count, taps, delay, iterations, out_offsets))
+    return rc;
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->run_host(audio, (long)total, reinterpret_cast<const long*>(offsets),
+                     reinterpret_cast<const long*>(lens), count, taps, delay, iterations, out,
+                     reinterpret_cast<const long*>(out_offsets));
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_wpe_set_budget(zasr_wpe* h, int64_t bytes) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  if (bytes <= 0) return fail(ZASR_ERR_INVALID, "WPE: the budget must be positive");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_budget((size_t)bytes);
+  return ZASR_OK;
+}
+
+int32_t zasr_wpe_last_groups(const zasr_wpe* h) { return h ? h->eng->last_groups() : 0; }
+
+int zasr_wpe_trim(zasr_wpe* h) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->trim();
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_wpe_set_profile(zasr_wpe* h, int32_t on) {
+  if (!h) return fail(ZASR_ERR_INVALID, "null handle");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  h->eng->set_profile(on != 0);
+  return ZASR_OK;
+}
+
+int zasr_wpe_stage_ms(zasr_wpe* h, float* ms3) {
+  if (!h || !ms3) return fail(ZASR_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lk(h->eng->mu);
+  std::memcpy(ms3, h->eng->stage_ms(), sizeof(float) * zasr::WpeEngine::kStages);
+  return ZASR_OK;
+}
+
+int zasr_selftest_wpe_stft(zasr_wpe* h, const float* signal, int64_t n, float* Y, float* max_sq) {
+  if (!h || !signal || !Y || !max_sq) return fail(ZASR_ERR_INVALID, "null argument");
+  if (n < 1 || n > zasr::kWpeMaxSamples) return fail(ZASR_ERR_INVALID, "WPE: n must be in 1..960000");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->selftest_stft(signal, (long)n, Y, max_sq);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_wpe_iter(zasr_wpe* h, const float* Y, int32_t T, int32_t taps, int32_t delay,
+                           float max_sq, const double* g_prev, double* g, float* X,
+                           float* next_max_sq) {
+  if (!h || !Y || !g) return fail(ZASR_ERR_INVALID, "null argument");
+  if (T < 1 || T > zasr::wpe_frames(zasr::kWpeMaxSamples))
+    return fail(ZASR_ERR_INVALID, "WPE: T out of range");
+  if (taps < 1 || taps > zasr::kWpeMaxTaps || delay < 1 || delay > zasr::kWpeMaxDelay)
+    return fail(ZASR_ERR_INVALID, "WPE: taps and delay must be in 1..16");
+  if (!(max_sq >= 0.f)) return fail(ZASR_ERR_INVALID, "WPE: max_sq must not be negative");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->selftest_iter(Y, T, taps, delay, max_sq, g_prev, g, X, next_max_sq);
+    return (int)ZASR_OK;
+  });
+}
+
+int zasr_selftest_wpe_istft(zasr_wpe* h, const float* X, int32_t T, int64_t n, float* out) {
+  if (!h || !X || !out) return fail(ZASR_ERR_INVALID, "null argument");
+  if (n < 1 || n > zasr::kWpeMaxSamples || T != zasr::wpe_frames((long)n))
+    return fail(ZASR_ERR_INVALID, "WPE: T must be zasr_wpe_frames(n), n in 1..960000");
+  return guarded([&]() {
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    h->eng->selftest_istft(X, T, (long)n, out);
     return (int)ZASR_OK;
   });
 }

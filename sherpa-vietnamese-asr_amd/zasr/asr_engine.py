@@ -32,6 +32,13 @@ worker -- is served from those results.  Batched results equal per-chunk results
 Chunks that are not views of a planned signal (WPE-processed copies, other callers) take
 the per-chunk path.  ZASR_PLAN_AHEAD=0 turns the routing off.
 
+With `install(..., audio_module=m, wpe=True)` and a caller whose config enables preprocess_wpe
+the plan is registered in WPE mode: its decode first dereverberates and peak-limits every chunk
+in one device batch (zasr.audio.apply_wpe_batch), decodes the packed result, and keeps the
+processed chunks; the rebound apply_wpe_dereverberation hands a worker the processed chunk of
+its span (tagged), adaptive_peak_limit passes the tag on, and decode_chunk serves a tagged
+chunk from the plan.
+
 The search and the word post-processing stay semantically identical to the reference;
 the arithmetic runs in libzasr (see DESIGN.md for precision modes and tolerances).
 """
@@ -456,7 +463,8 @@ class _PlannedSignal:
     background the moment the plan is registered (for the recognizers already loaded, which
     the reference creates before it plans, :2041-2057), or on the first chunk asked for."""
 
-    def __init__(self, audio: np.ndarray, plan, d_audio=None):
+    def __init__(self, audio: np.ndarray, plan, d_audio=None, wpe: Optional[dict] = None,
+                 device_id: Optional[int] = None):
         # when the pipeline drops the signal, the entry goes with it (its HBM copy and the
         # plan's results): _prune_planned runs from the weakref callback
         self.ref = weakref.ref(audio, lambda _r: _prune_planned())
@@ -468,6 +476,13 @@ class _PlannedSignal:
         self.lock = threading.Lock()
         self.jobs = weakref.WeakKeyDictionary()  # handle -> {beam: _PlanDecode}
         self.running = 0
+        # WPE mode (wpe = the keyword arguments of apply_wpe_dereverberation): the plan decodes
+        # the dereverberated, peak-limited chunks, made once per signal by _wpe_chunks
+        self.wpe = dict(wpe) if wpe is not None else None
+        self.device_id = device_id
+        self._wpe_lock = threading.Lock()
+        self._wpe_state = None  # (packed device tensor | None, offsets, {span: chunk}) | error
+        self._wpe_logged = False
 
     def alive(self) -> bool:
         return self.ref() is not None
@@ -481,6 +496,17 @@ class _PlannedSignal:
         res = {}
         sizes = [min(PLAN_BATCH_CHUNKS, len(self.plan) - i)
                  for i in range(0, len(self.plan), PLAN_BATCH_CHUNKS)]
+        if self.wpe is not None:
+            packed, off, chunks = self._wpe_chunks()
+            if packed is not None and getattr(handle, "device_id", None) == packed.device.index:
+                out = handle.decode_device_batches(packed.data_ptr(), [int(o) for o in off[:-1]],
+                                                   [e - s for s, e in self.plan], sizes, beam=beam)
+                res.update(zip(self.plan, out))
+            else:
+                for i in range(0, len(self.plan), PLAN_BATCH_CHUNKS):
+                    part = self.plan[i:i + PLAN_BATCH_CHUNKS]
+                    res.update(zip(part, handle.decode([chunks[sp] for sp in part], beam=beam)))
+            return res
         d_audio = self.d_audio
         if d_audio is not None and getattr(handle, "device_id", None) == d_audio.device.index:
             out = handle.decode_device_batches(d_audio.data_ptr(), [s for s, _ in self.plan],
@@ -491,6 +517,39 @@ class _PlannedSignal:
                 part = self.plan[i:i + PLAN_BATCH_CHUNKS]
                 res.update(zip(part, handle.decode([audio[s:e] for s, e in part], beam=beam)))
         return res
+
+    def _wpe_chunks(self):
+        """WPE mode: (packed device tensor or None, offsets, {span: processed host chunk}) of the
+        whole plan, dereverberated and peak-limited in one device batch, made on first use and
+        kept while the signal lives.  Raises what the batch raised, every time."""
+        with self._wpe_lock:
+            if self._wpe_state is None:
+                try:
+                    audio = self.ref()
+                    if audio is None:
+                        raise RuntimeError("the planned signal is gone")
+                    src = self.d_audio if self.d_audio is not None else audio
+                    packed, off, host = _wpe_batch(src, self.plan, self.wpe, self.device_id)
+                    chunks = {sp: host[int(off[i]):int(off[i + 1])]
+                              for i, sp in enumerate(self.plan)}
+                    self._wpe_state = (packed, off, chunks)
+                except BaseException as e:
+                    self._wpe_state = e
+            if isinstance(self._wpe_state, BaseException):
+                raise self._wpe_state
+            return self._wpe_state
+
+    def processed(self, span):
+        """WPE mode: the processed chunk of `span`, or None when the batch failed (logged once;
+        the caller then processes its chunk on its own)."""
+        try:
+            return self._wpe_chunks()[2].get(span)
+        except BaseException as e:
+            with self.lock:
+                first, self._wpe_logged = not self._wpe_logged, True
+            if first:
+                logger.warning(f"[zasr] WPE plan batch failed, chunks are processed one by one: {e!r}")
+            return None
 
     def start(self, handle, beam: int) -> "_PlanDecode":
         with self.lock:
@@ -510,6 +569,9 @@ class _PlannedSignal:
             self.running -= 1
             if self.running == 0:
                 self.d_audio = None
+                with self._wpe_lock:  # the packed chunks' HBM copy goes too; the host chunks stay
+                    if isinstance(self._wpe_state, tuple):
+                        self._wpe_state = (None,) + self._wpe_state[1:]
 
     def result(self, handle, beam: int, span):
         """The plan's result for `span`, or None when the plan's decode failed (logged once;
@@ -563,6 +625,80 @@ class _PlanDecode:
 _plan_lock = threading.RLock()  # re-entered by the signal weakref callback
 _planned: List[_PlannedSignal] = []
 _feat_src: Dict[int, tuple] = {}  # id(features) -> (weakref(features), chunk data ptr, samples)
+_wpe_src: Dict[int, tuple] = {}  # id(chunk) -> (weakref(chunk), weakref(planned signal), span)
+_wpe_plan = False  # zasr.dropin.install(..., wpe=True): plans of WPE callers decode in WPE mode
+WPE_DEFAULTS = {"sample_rate": 16000, "fft_size": 512, "hop_size": 128, "taps": 10, "delay": 3,
+                "iterations": 3}
+
+
+def set_wpe_plan(on: bool) -> None:
+    global _wpe_plan
+    _wpe_plan = bool(on)
+
+
+def wpe_plan_on() -> bool:
+    return _wpe_plan and _plan_ahead_on()
+
+
+def _wpe_batch(src, plan, wpe: dict, device_id: Optional[int]):
+    """The plan's chunks of src (the host signal or its HBM copy) through
+    zasr.audio.apply_wpe_batch with the peak limiter: (packed device tensor, offsets, the packed
+    chunks on the host)."""
+    import torch
+    from zasr import audio as za
+    dev = src.device.index if hasattr(src, "device") and hasattr(src, "is_cuda") else (
+        int(os.environ.get("ZASR_DEVICE", "0")) if device_id is None else int(device_id))
+    with torch.cuda.device(dev):
+        packed, off = za.apply_wpe_batch(src, plan, peak_limit=True, device_out=True, **wpe)
+        return packed, off, packed.cpu().numpy()
+
+
+def _tag_wpe(chunk, sig: "_PlannedSignal", span) -> None:
+    key = id(chunk)
+
+    def drop(_, k=key):
+        _wpe_src.pop(k, None)
+    _wpe_src[key] = (weakref.ref(chunk, drop), weakref.ref(sig), span)
+
+
+def _wpe_tag(chunk):
+    """(planned signal, span) of a chunk the rebound apply_wpe_dereverberation handed out (or the
+    limiter made of one), else None."""
+    src = _wpe_src.get(id(chunk))
+    if src is None or src[0]() is not chunk:
+        return None
+    sig = src[1]()
+    return None if sig is None or not sig.alive() else (sig, src[2])
+
+
+def wpe_dereverberation_planned(audio, sample_rate=16000, fft_size=512, hop_size=128, taps=10,
+                                delay=3, iterations=3):
+    """The drop-in's apply_wpe_dereverberation (core/audio_preprocessing.py:157-216): a view of a
+    signal planned in WPE mode at one of the plan's spans gets that span's chunk of the plan's one
+    device batch (already peak-limited, tagged for decode_chunk); anything else is processed on
+    its own by zasr.audio.apply_wpe_dereverberation."""
+    from zasr import audio as za
+    kw = {"sample_rate": sample_rate, "fft_size": fft_size, "hop_size": hop_size, "taps": taps,
+          "delay": delay, "iterations": iterations}
+    hit = _planned_span(audio, wpe=True) if _plan_ahead_on() else None
+    if hit is not None and hit[0].wpe == kw:
+        chunk = hit[0].processed(hit[1])
+        if chunk is not None:
+            _tag_wpe(chunk, hit[0], hit[1])
+            return chunk
+    return za.apply_wpe_dereverberation(audio, **kw)
+
+
+def peak_limit_planned(audio, target_peak=0.95):
+    """The drop-in's adaptive_peak_limit (core/audio_preprocessing.py:226-243) when WPE is
+    installed: zasr.audio's, and whatever it returns for a tagged chunk carries the tag on (the
+    plan's chunks are limited already, so decode_chunk still finds the span)."""
+    from zasr import audio as za
+    out = za.adaptive_peak_limit(audio, target_peak)
+    tag = _wpe_tag(audio) if target_peak == 0.95 else None
+    if tag is not None and out is not audio and isinstance(out, np.ndarray):
+        _tag_wpe(out, tag[0], tag[1])
+    return out
 
 
 def _plan_ahead_on() -> bool:
@@ -605,15 +741,17 @@ def _prune_planned() -> None:
         _planned[:] = [p for p in _planned if p.alive()]
 
 
-def register_plan(audio, plan, d_audio=None, start: bool = True) -> bool:
+def register_plan(audio, plan, d_audio=None, start: bool = True, wpe: Optional[dict] = None,
+                  device_id: Optional[int] = None) -> bool:
     """Remember that `audio` (the signal the planner worked on) is cut into `plan`
     [(start, end, overlap)]; chunks decode_chunk later receives as views of it at those spans
     are served from one batched decode of the plan, started now for the loaded recognizers.
     `d_audio`: the signal's HBM copy (a torch tensor), when the GPU planner made one.  Keeps
-    the last few signals (weakly)."""
+    the last few signals (weakly).  `wpe`: register in WPE mode with these arguments of
+    apply_wpe_dereverberation (the plan then decodes the processed chunks)."""
     if not _plan_ahead_on() or not _is_f32_vector(audio) or not plan:
         return False
-    sig = _PlannedSignal(audio, plan, d_audio)
+    sig = _PlannedSignal(audio, plan, d_audio, wpe, device_id)
     with _plan_lock:
         _planned[:] = [p for p in _planned if p.alive()][-3:] + [sig]
     if start:
@@ -623,14 +761,15 @@ def register_plan(audio, plan, d_audio=None, start: bool = True) -> bool:
 
 
 def register_plan_from_regions(audio, regions, best_split_fn=None, d_audio=None,
-                               start: bool = True) -> bool:
+                               start: bool = True, wpe: Optional[dict] = None,
+                               device_id: Optional[int] = None) -> bool:
     """The find_silent_regions hook: the plan the reference builds from these regions
     (:2141-2161, zasr.plan.plan_from_regions with the reference's own find_best_split_point)."""
     from zasr.plan import plan_from_regions
     if not _is_f32_vector(audio):
         return False
     return register_plan(audio, plan_from_regions(int(audio.shape[0]), regions, best_split_fn),
-                         d_audio, start)
+                         d_audio, start, wpe, device_id)
 
 
 def _gpu_planner_on() -> bool:
@@ -657,7 +796,7 @@ def silent_regions_device(audio: np.ndarray, device_id: int = 0):
     return regions_from_flags(flags.cpu().numpy().astype(bool), FRAME_LEN, n, MIN_SILENCE_SEC), d
 
 
-def plan_ahead_regions(audio, best_split_fn=None, start: bool = True):
+def plan_ahead_regions(audio, best_split_fn=None, start: bool = True, wpe: Optional[dict] = None):
     """The drop-in's find_silent_regions for the planner's default-argument calls
     (:2139, :2183): the regions from the GPU silence detector (bit-identical to the
     reference's), with the plan built from them registered and its decode started (unless
@@ -669,20 +808,21 @@ def plan_ahead_regions(audio, best_split_fn=None, start: bool = True):
     dev = handles[0][0].device_id if handles else int(os.environ.get("ZASR_DEVICE", "0"))
     regions, d = silent_regions_device(audio, dev)
     register_plan_from_regions(audio, regions, best_split_fn, d_audio=d if start else None,
-                               start=start)
+                               start=start, wpe=wpe, device_id=dev)
     return regions
 
 
-def _planned_span(chunk):
+def _planned_span(chunk, wpe: bool = False):
     """(planned signal, (start, end)) when `chunk` is a view of a registered signal at one of
-    its plan's spans, else None."""
+    its plan's spans, else None.  A signal planned in WPE mode matches only with wpe=True (its
+    plan's results are those of the processed chunks, not of the raw views)."""
     if not _is_f32_vector(chunk) or chunk.shape[0] == 0:
         return None
     p = chunk.__array_interface__["data"][0]
     with _plan_lock:
         sigs = list(_planned)
     for sig in reversed(sigs):
-        if sig.ref() is None:
+        if sig.ref() is None or (sig.wpe is not None) != wpe:
             continue
         off = p - sig.ptr
         if off >= 0 and off % 4 == 0:
@@ -715,7 +855,7 @@ def _planned_result(handle, beam, audio_chunk, precomputed_features):
                 or src[1] != audio_chunk.__array_interface__["data"][0]
                 or src[2] != audio_chunk.shape[0]):
             return None
-    hit = _planned_span(audio_chunk)
+    hit = _wpe_tag(audio_chunk) or _planned_span(audio_chunk)
     if hit is None:
         return None
     return hit[0].result(handle, beam, hit[1])

@@ -11,7 +11,12 @@ What it stands in for:
   core/asr_engine.py:512-516   the quiet-file boost audio / peak * 0.95         -> boost_quiet
   core/audio_preprocessing.py  compute_segment_rms, per_segment_rms_normalize,
                                adaptive_peak_limit, preprocess_audio (:39-140, :226-293), same
-                               names and signatures; apply_wpe_dereverberation is not covered
+                               names and signatures
+  core/audio_preprocessing.py  apply_wpe_dereverberation (:157-216), same name and signature:
+                               the per-frequency WPE of DESIGN.md §4k (the documented
+                               algorithm; the reference's own call stacks the 257 bins as
+                               channels and is not reproduced, so installing it is opt-in);
+                               apply_wpe_batch runs every chunk of a file in one device call
 
 Every function takes a numpy array and returns numpy float32, or takes a torch CUDA tensor
 and returns one (nothing then leaves the device but the per-segment sums and the peak).  The
@@ -28,11 +33,12 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from zasr.binding import AudioFrontEnd, ZasrError, audio_out_len
+from zasr.binding import AudioFrontEnd, WpeEngine, ZasrError, audio_out_len
 
 logger = logging.getLogger("zasr")
 
 _fronts: dict = {}
+_wpes: dict = {}
 _lock = threading.Lock()
 
 
@@ -54,11 +60,25 @@ def front_end(device_id: Optional[int] = None) -> AudioFrontEnd:
         return fe
 
 
+def wpe_engine(device_id: Optional[int] = None) -> WpeEngine:
+    """The process-wide WPE engine of one device (its tables and workspace are cached)."""
+    torch = _torch()
+    dev = torch.cuda.current_device() if device_id is None else int(device_id)
+    with _lock:
+        we = _wpes.get(dev)
+        if we is None or not we.handle:
+            we = _wpes[dev] = WpeEngine(dev)
+        return we
+
+
 def close() -> None:
     with _lock:
         for fe in _fronts.values():
             fe.close()
         _fronts.clear()
+        for we in _wpes.values():
+            we.close()
+        _wpes.clear()
 
 
 def _stream() -> int:
@@ -347,6 +367,96 @@ def preprocess_audio(audio, vad_segments, sample_rate=16000, enable_rms_normaliz
                      enable_rms_normalize=enable_rms_normalize)
     emit("PHASE:Preprocess|Preprocessing hoàn tất|100")
     return _back(d, was_tensor)
+
+
+# ---- WPE dereverberation (core/audio_preprocessing.py:157-216) -----------------
+
+WPE_FFT, WPE_HOP, WPE_MAX_SAMPLES = 512, 128, 60 * 16000
+
+
+def _check_wpe(sample_rate, fft_size, hop_size, taps, delay, iterations) -> None:
+    if int(fft_size) != WPE_FFT or int(hop_size) != WPE_HOP:
+        raise ValueError("the device WPE supports fft_size=512, hop_size=128 only")
+    if int(sample_rate) != 16000:
+        raise ValueError("the device WPE runs on the 16 kHz signal")
+    if not 1 <= int(taps) <= 16:
+        raise ValueError("taps must be in 1..16")
+    if not 1 <= int(delay) <= 16:
+        raise ValueError("delay must be in 1..16")
+    if not 1 <= int(iterations) <= 8:
+        raise ValueError("iterations must be in 1..8")
+
+
+def apply_wpe_batch(signal, spans, sample_rate=16000, fft_size=512, hop_size=128, taps=10, delay=3,
+                    iterations=3, peak_limit: bool = False, device_out: bool = False,
+                    target_peak=0.95):
+    """apply_wpe_dereverberation on signal[start:end] for every (start, end) of spans, all in
+    one device call; signal is numpy or a torch CUDA tensor (float32, mono).  A chunk's result
+    is bit-identical to running it alone.  peak_limit applies adaptive_peak_limit
+    (core/audio_preprocessing.py:226-243) to every chunk afterwards, on the device, bit-identical
+    to zasr.audio.adaptive_peak_limit on that chunk.  Returns the list of float32 arrays (CUDA
+    tensors for a tensor input), or with device_out (packed float32 CUDA tensor, int64 offsets
+    [len(spans) + 1]): chunk c is packed[offsets[c]:offsets[c + 1]]."""
+    torch = _torch()
+    _check_wpe(sample_rate, fft_size, hop_size, taps, delay, iterations)
+    tensor_in = _is_tensor(signal)
+    if tensor_in:
+        if not signal.is_cuda:
+            raise ValueError("a torch input must be a CUDA tensor")
+        d = signal.to(torch.float32).contiguous()
+    else:
+        a = np.ascontiguousarray(signal, np.float32)
+        if a.ndim != 1:
+            raise ValueError("audio must be mono: shape [n]")
+        d = torch.from_numpy(a).cuda()
+    if d.ndim != 1:
+        raise ValueError("audio must be mono: shape [n]")
+    total = int(d.numel())
+    spans = [(int(s), int(e)) for s, e in spans]
+    for s, e in spans:
+        if s < 0 or e < s or e > total:
+            raise ValueError(f"span ({s}, {e}) outside the signal of {total} samples")
+        if e - s > WPE_MAX_SAMPLES:
+            raise ValueError("a chunk is at most 60 s (960000 samples)")
+    lens = np.array([e - s for s, e in spans], np.int64)
+    offsets = np.zeros(len(spans) + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    packed = torch.empty(max(int(offsets[-1]), 1), dtype=torch.float32, device=d.device)
+    st = _stream()
+    if spans:
+        wpe_engine().run_device(d.data_ptr(), total, [s for s, _ in spans], lens, packed.data_ptr(),
+                                offsets[:-1], taps, delay, iterations, st)
+        if peak_limit:
+            fe = front_end()
+            for c in range(len(spans)):
+                n = int(lens[c])
+                if n == 0:
+                    continue
+                ptr = packed.data_ptr() + 4 * int(offsets[c])
+                peak = fe.peak(ptr, n, st)
+                if peak > target_peak:
+                    _limit_device(fe, ptr, n, peak, target_peak, st)
+    packed = packed[:int(offsets[-1])]
+    if device_out:
+        return packed, offsets
+    chunks = [packed[int(offsets[c]):int(offsets[c + 1])] for c in range(len(spans))]
+    if tensor_in:
+        return [c.clone() for c in chunks]
+    host = packed.cpu().numpy()
+    return [host[int(offsets[c]):int(offsets[c + 1])].copy() for c in range(len(spans))]
+
+
+def apply_wpe_dereverberation(audio, sample_rate=16000, fft_size=512, hop_size=128, taps=10,
+                              delay=3, iterations=3):
+    """core/audio_preprocessing.py:157-216, per frequency bin.  numpy in, numpy
+    float32 out; a torch CUDA tensor in, one out.  A signal under 2 * fft_size samples comes
+    back as the same object (:188-189)."""
+    _check_wpe(sample_rate, fft_size, hop_size, taps, delay, iterations)
+    n = int(audio.shape[0]) if hasattr(audio, "shape") else len(audio)
+    if n < 2 * int(fft_size):
+        return audio
+    return apply_wpe_batch(audio, [(0, n)], sample_rate, fft_size, hop_size, taps, delay,
+                           iterations)[0]
 
 
 AUDIO_NAMES = ("compute_segment_rms", "per_segment_rms_normalize", "adaptive_peak_limit",

@@ -66,6 +66,10 @@ EXPORTS = (
     "zasr_audio_create", "zasr_audio_destroy", "zasr_audio_out_len", "zasr_audio_resample_taps",
     "zasr_audio_to_16k", "zasr_audio_peak", "zasr_audio_scale", "zasr_audio_segment_sumsq",
     "zasr_audio_apply_gain",
+    "zasr_wpe_create", "zasr_wpe_destroy", "zasr_wpe_frames", "zasr_wpe_run_device", "zasr_wpe_run",
+    "zasr_wpe_set_budget", "zasr_wpe_last_groups", "zasr_wpe_trim", "zasr_wpe_set_profile",
+    "zasr_wpe_stage_ms", "zasr_selftest_wpe_stft", "zasr_selftest_wpe_iter",
+    "zasr_selftest_wpe_istft",
     "zasr_diar_create", "zasr_diar_destroy", "zasr_diar_similarity", "zasr_diar_prune",
     "zasr_diar_eigs", "zasr_diar_spectral_embed", "zasr_diar_last_stats",
     "zasr_clu_create", "zasr_clu_destroy", "zasr_clu_ahc", "zasr_clu_last_stats",
@@ -449,7 +453,28 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.zasr_audio_segment_sumsq.restype = C.c_int
     lib.zasr_audio_apply_gain.argtypes = [P, P, I64, i64p, i64p, fp, i64p, I32, fp, I64, fp, P]
     lib.zasr_audio_apply_gain.restype = C.c_int
+    # WPE dereverberation (zasr/audio.py)
     dp, DBL = C.POINTER(C.c_double), C.c_double
+    lib.zasr_wpe_create.argtypes = [I32, C.POINTER(P)]
+    lib.zasr_wpe_destroy.argtypes = [P]
+    lib.zasr_wpe_destroy.restype = None
+    lib.zasr_wpe_frames.argtypes = [I64]
+    lib.zasr_wpe_frames.restype = I64
+    lib.zasr_wpe_run_device.argtypes = [P, P, I64, i64p, i64p, I32, I32, I32, I32, P, i64p, P]
+    lib.zasr_wpe_run.argtypes = [P, fp, I64, i64p, i64p, I32, I32, I32, I32, fp, i64p]
+    lib.zasr_wpe_set_budget.argtypes = [P, I64]
+    lib.zasr_wpe_last_groups.argtypes = [P]
+    lib.zasr_wpe_last_groups.restype = I32
+    lib.zasr_wpe_trim.argtypes = [P]
+    lib.zasr_wpe_set_profile.argtypes = [P, I32]
+    lib.zasr_wpe_stage_ms.argtypes = [P, fp]
+    lib.zasr_selftest_wpe_stft.argtypes = [P, fp, I64, fp, fp]
+    lib.zasr_selftest_wpe_iter.argtypes = [P, fp, I32, I32, I32, C.c_float, dp, dp, fp, fp]
+    lib.zasr_selftest_wpe_istft.argtypes = [P, fp, I32, I64, fp]
+    for _n in ("wpe_create", "wpe_run_device", "wpe_run", "wpe_set_budget", "wpe_trim",
+               "wpe_set_profile", "wpe_stage_ms", "selftest_wpe_stft", "selftest_wpe_iter",
+               "selftest_wpe_istft"):
+        getattr(lib, "zasr_" + _n).restype = C.c_int
     lib.zasr_diar_create.argtypes = [I32, C.POINTER(P)]
     lib.zasr_diar_create.restype = C.c_int
     lib.zasr_diar_destroy.argtypes = [P]
@@ -2505,6 +2530,142 @@ class AudioFrontEnd:
             pe.ctypes.data_as(i64), pg.ctypes.data_as(C_FP), po.ctypes.data_as(i64), pb.size,
             rv.ctypes.data_as(C_FP), rv.size, C.byref(v), C.c_void_p(stream)))
         return np.float32(v.value)
+
+
+class WpeEngine:
+    """WPE dereverberation on the GPU (include/zasr.h zasr_wpe_*): every chunk of a
+    file in one call, each frequency bin on its own.  zasr/audio.py is the numpy / torch surface
+    over this class; the selftest_* methods run one kernel on one chunk's host operands."""
+
+    STAGES = ("stft", "iterations", "istft")
+    BINS = 257
+
+    def __init__(self, device_id: int = 0, lib_path: Optional[str] = None):
+        self.lib = load_library(lib_path)
+        h = C.c_void_p()
+        if self.lib.zasr_wpe_create(int(device_id), C.byref(h)) != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+        self.handle = h
+        self.device_id = int(device_id)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.zasr_wpe_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ZasrError(self.lib.zasr_last_error().decode())
+
+    def trim(self) -> None:
+        self._check(self.lib.zasr_wpe_trim(self.handle))
+
+    def set_budget(self, nbytes: int) -> None:
+        """Spectrum bytes one launch group may take (default 2 GiB).  Results do not change."""
+        self._check(self.lib.zasr_wpe_set_budget(self.handle, int(nbytes)))
+
+    @property
+    def last_groups(self) -> int:
+        return int(self.lib.zasr_wpe_last_groups(self.handle))
+
+    def set_profile(self, on: bool) -> None:
+        self._check(self.lib.zasr_wpe_set_profile(self.handle, int(bool(on))))
+
+    def stage_ms(self) -> dict:
+        ms = (C.c_float * 3)()
+        self._check(self.lib.zasr_wpe_stage_ms(self.handle, ms))
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+    @staticmethod
+    def _spans(offsets, lens, out_offsets):
+        o = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        n = np.ascontiguousarray(lens, np.int64).reshape(-1)
+        if out_offsets is None:
+            out_offsets = np.concatenate([[0], np.cumsum(np.clip(n, 0, None))[:-1]]) if n.size else n
+        q = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if not (o.shape == n.shape == q.shape):
+            raise ValueError("offsets, lens and out_offsets differ in length")
+        return o, n, q
+
+    def run_device(self, d_audio: int, total: int, offsets, lens, d_out: int, out_offsets=None,
+                   taps: int = 10, delay: int = 3, iterations: int = 3, stream: int = 0) -> np.ndarray:
+        """Chunks [offsets[c], offsets[c] + lens[c]) of the device signal d_audio[0, total) ->
+        device pointer d_out at out_offsets (default: packed in order).  Returns out_offsets."""
+        o, n, q = self._spans(offsets, lens, out_offsets)
+        ip = C.POINTER(C.c_int64)
+        self._check(self.lib.zasr_wpe_run_device(
+            self.handle, C.c_void_p(d_audio), int(total), o.ctypes.data_as(ip), n.ctypes.data_as(ip),
+            o.size, int(taps), int(delay), int(iterations), C.c_void_p(d_out), q.ctypes.data_as(ip),
+            C.c_void_p(stream)))
+        return q
+
+    def run(self, audio: np.ndarray, offsets, lens, taps: int = 10, delay: int = 3,
+            iterations: int = 3) -> List[np.ndarray]:
+        """The same on a host signal: the chunks' float32 outputs."""
+        a = np.ascontiguousarray(audio, np.float32).reshape(-1)
+        o, n, q = self._spans(offsets, lens, None)
+        out = np.zeros(max(1, int(np.clip(n, 0, None).sum())), np.float32)
+        ip = C.POINTER(C.c_int64)
+        self._check(self.lib.zasr_wpe_run(
+            self.handle, a.ctypes.data_as(C_FP), a.size, o.ctypes.data_as(ip), n.ctypes.data_as(ip),
+            o.size, int(taps), int(delay), int(iterations), out.ctypes.data_as(C_FP),
+            q.ctypes.data_as(ip)))
+        return [out[int(b):int(b) + int(m)] for b, m in zip(q, n)]
+
+    def selftest_stft(self, signal):
+        """wpe_stft alone: (Y [257][T] complex64, max |Y|^2)."""
+        x = np.ascontiguousarray(signal, np.float32).reshape(-1)
+        T = wpe_frames(x.size)
+        Y = np.empty((self.BINS, T), np.complex64)
+        mx = C.c_float()
+        self._check(self.lib.zasr_selftest_wpe_stft(
+            self.handle, x.ctypes.data_as(C_FP), x.size, Y.ctypes.data_as(C_FP), C.byref(mx)))
+        return Y, np.float32(mx.value)
+
+    def selftest_iter(self, Y, max_sq, taps: int = 10, delay: int = 3, g_prev=None, want_x: bool = True):
+        """wpe_iter alone on Y [257][T]: (g [257][taps] complex128, X [T][257] complex64 or None,
+        max |X|^2)."""
+        Y = np.ascontiguousarray(Y, np.complex64)
+        if Y.ndim != 2 or Y.shape[0] != self.BINS:
+            raise ValueError("Y must be [257][T]")
+        T = Y.shape[1]
+        gp = None if g_prev is None else np.ascontiguousarray(g_prev, np.complex128)
+        if gp is not None and gp.shape != (self.BINS, taps):
+            raise ValueError("g_prev must be [257][taps]")
+        g = np.empty((self.BINS, taps), np.complex128)
+        X = np.empty((T, self.BINS), np.complex64) if want_x else None
+        nm = C.c_float()
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.zasr_selftest_wpe_iter(
+            self.handle, Y.ctypes.data_as(C_FP), T, int(taps), int(delay), float(np.float32(max_sq)),
+            None if gp is None else gp.ctypes.data_as(dp), g.ctypes.data_as(dp),
+            None if X is None else X.ctypes.data_as(C_FP), C.byref(nm)))
+        return g, X, np.float32(nm.value)
+
+    def selftest_istft(self, X, n: int) -> np.ndarray:
+        """wpe_istft alone on X [T][257], T = wpe_frames(n): the n output samples."""
+        X = np.ascontiguousarray(X, np.complex64)
+        if X.ndim != 2 or X.shape[1] != self.BINS:
+            raise ValueError("X must be [T][257]")
+        out = np.empty(int(n), np.float32)
+        self._check(self.lib.zasr_selftest_wpe_istft(
+            self.handle, X.ctypes.data_as(C_FP), X.shape[0], int(n), out.ctypes.data_as(C_FP)))
+        return out
+
+
+def wpe_frames(n: int, lib_path: Optional[str] = None) -> int:
+    """STFT frames of a chunk of n samples (zasr_wpe_frames, host only)."""
+    lib = load_library(lib_path)
+    T = int(lib.zasr_wpe_frames(int(n)))
+    if T < 0:
+        raise ValueError(lib.zasr_last_error().decode())
+    return T
 
 
 class Diarizer:

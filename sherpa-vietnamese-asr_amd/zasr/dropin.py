@@ -11,6 +11,9 @@
     # optional: preprocess_audio's level conditioning on the GPU (zasr.audio)
     import core.audio_preprocessing
     install(core.asr_engine, audio_module=core.audio_preprocessing)
+    # optional, and not the reference's numbers: WPE dereverberation on the GPU, per frequency
+    # bin as documented, with the plan-ahead decode kept for preprocess_wpe
+    install(core.asr_engine, audio_module=core.audio_preprocessing, wpe=True)
 
 This build's modules live in the `zasr` package, so importing them never shadows the
 reference's `core` package (both trees can be on sys.path in any order).
@@ -42,7 +45,15 @@ What is rebound (the ASR hot path, core/asr_engine.py:698-1326):
                   per_segment_rms_normalize, adaptive_peak_limit, preprocess_audio
                   (core/asr_engine.py:2101 imports preprocess_audio from the module at call
                   time, so the rebound name is the one it gets); apply_wpe_dereverberation
-                  stays the reference's
+                  stays the reference's unless wpe=True
+  audio_preprocessing  (only with wpe=True) apply_wpe_dereverberation (imported from the module
+                  at call time, core/asr_engine.py:2225-2229, :2338-2342, :2427-2430) and
+                  adaptive_peak_limit in its tag-passing form: a caller whose config enables
+                  preprocess_wpe then has its plan decoded in WPE mode (every chunk
+                  dereverberated and peak-limited in one device batch, then ONE decode), and
+                  the workers' per-chunk calls are served from it.  The device WPE is the
+                  per-frequency algorithm, not the reference's (1, F, T) call: results differ
+                  from the reference's, which is why this switch is separate
 
 get_ort, TranscriberPipeline, the overlap merge, ROVER vote and UI glue stay the
 reference's.  create_recognizer reads the hotword file and score through the reference
@@ -67,6 +78,9 @@ VAD_NAMES = ("_get_vad_session", "unload_vad_model", "get_cached_vad_probs",
 VAD_ENGINE_NAMES = ("get_vad_segments", "unload_vad_model")
 AUDIO_NAMES = ("compute_segment_rms", "per_segment_rms_normalize", "adaptive_peak_limit",
                "preprocess_audio")
+# wpe=True: the reference's name -> zasr.asr_engine's plan-aware function
+WPE_NAMES = {"apply_wpe_dereverberation": "wpe_dereverberation_planned",
+             "adaptive_peak_limit": "peak_limit_planned"}
 
 
 def _caller_uses_wpe(frame) -> bool:
@@ -82,12 +96,15 @@ def _caller_uses_wpe(frame) -> bool:
 def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None,
             calibration_module: Optional[ModuleType] = None,
             vad_module: Optional[ModuleType] = None,
-            audio_module: Optional[ModuleType] = None) -> List[str]:
+            audio_module: Optional[ModuleType] = None, wpe: bool = False) -> List[str]:
     from zasr import asr_engine as ours
     from zasr import calibration as ours_cal
     from zasr import hardware_accel as ours_hw
     if engine_module is ours:
         raise ValueError("install() needs the reference's core.asr_engine module, got zasr's own")
+    if wpe and audio_module is None:
+        raise ValueError("install(wpe=True) needs audio_module (the reference's "
+                         "core.audio_preprocessing): its apply_wpe_dereverberation is rebound")
     done = []
     for n in ENGINE_NAMES:
         setattr(engine_module, n, getattr(ours, n))
@@ -107,11 +124,14 @@ def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None
 
         def find_silent_regions(audio_data, *args, **kwargs):
             # with preprocess_wpe the workers decode WPE-processed copies, never views of the
-            # planned signal (:2248, :2338-2341): register the plan, start no decode for it
-            start = not _caller_uses_wpe(sys._getframe(1))
+            # planned signal (:2248, :2338-2341): register the plan, start no decode for it --
+            # unless install(wpe=True) rebound the WPE: then the plan runs in WPE mode
+            uses_wpe = _caller_uses_wpe(sys._getframe(1))
+            mode = dict(ours.WPE_DEFAULTS) if uses_wpe and ours.wpe_plan_on() else None
+            start = not uses_wpe or mode is not None
             if not args and not kwargs:  # the planner's calls (:2139, :2183) use the defaults
                 try:  # the GPU silence detector: same regions, plan registered + decoding
-                    regions = ours.plan_ahead_regions(audio_data, split_fn, start=start)
+                    regions = ours.plan_ahead_regions(audio_data, split_fn, start=start, wpe=mode)
                     if regions is not None:
                         return regions
                 except Exception as e:  # routing is an optimisation: never break the caller
@@ -119,7 +139,8 @@ def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None
             regions = orig_fsr(audio_data, *args, **kwargs)
             if not args and not kwargs:
                 try:
-                    ours.register_plan_from_regions(audio_data, regions, split_fn, start=start)
+                    ours.register_plan_from_regions(audio_data, regions, split_fn, start=start,
+                                                    wpe=mode)
                 except Exception as e:
                     ours.logger.warning(f"[zasr] plan registration skipped: {e}")
             return regions
@@ -128,6 +149,7 @@ def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None
         engine_module.find_silent_regions = find_silent_regions
         done.append("asr_engine.find_silent_regions")
     ours.set_host_module(engine_module)
+    ours.set_wpe_plan(wpe)
     if accel_module is not None:
         for n in ACCEL_NAMES:
             setattr(accel_module, n, getattr(ours_hw, n))
@@ -161,4 +183,9 @@ def install(engine_module: ModuleType, accel_module: Optional[ModuleType] = None
         for n in AUDIO_NAMES:
             setattr(audio_module, n, getattr(ours_audio, n))
             done.append("audio_preprocessing." + n)
+        if wpe:
+            for n, mine in WPE_NAMES.items():
+                setattr(audio_module, n, getattr(ours, mine))
+                if "audio_preprocessing." + n not in done:
+                    done.append("audio_preprocessing." + n)
     return done

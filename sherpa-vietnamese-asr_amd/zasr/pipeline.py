@@ -228,12 +228,15 @@ class FullPipe:
         return out, self.punct.runs - r0, self.punct.rows_run[n0:]
 
     def prepare(self, audio: np.ndarray, sample_rate: int = 16000, vad_segments=None,
-                rms_normalize: bool = False, condition: bool = False) -> None:
+                rms_normalize: bool = False, condition: bool = False, wpe: bool = False) -> None:
         """audio: the 16 kHz mono float32 signal (the defaults), or raw PCM for the device
         audio front end (zasr.audio): [n] or [n, C], float32 or int16, at sample_rate.  Then
         the signal in HBM is made by the front end, with the reference's quiet-file boost
         and preprocess_audio(vad_segments, enable_rms_normalize=rms_normalize) applied when
-        `condition` is set, and copied back once for the chunk planner (host logic)."""
+        `condition` is set, and copied back once for the chunk planner (host logic).  With `wpe`
+        (the reference's preprocess_wpe, core/asr_engine.py:2225-2229; off by default) the
+        decode chunks are dereverberated and peak-limited in one device batch
+        (zasr.audio.apply_wpe_batch) and the decode reads those."""
         import torch
         from zasr.plan import plan_chunks
         raw = np.asarray(audio)
@@ -287,6 +290,14 @@ class FullPipe:
         self.d_audio = d_front if front else torch.from_numpy(a).cuda()
         if d_early is not None:
             self.d_audio = d_early
+        # what the decode reads: the signal at the plan's offsets, or the packed WPE chunks
+        self.d_decode, self.c_decode_off = self.d_audio, self.c_off
+        if wpe and self.c_len:
+            from zasr import audio as fe
+            self.d_decode, off = fe.apply_wpe_batch(
+                self.d_audio, [(s, s + n) for s, n in zip(self.c_off, self.c_len)],
+                peak_limit=True, device_out=True)
+            self.c_decode_off = [int(o) for o in off[:-1]]
         self.d_feats = torch.empty((self.cap, 150, 80), dtype=torch.float32, device="cuda")
         self.d_emb = torch.empty((self.cap, self.emb.dim), dtype=torch.float32, device="cuda")
         self.s_campp = torch.cuda.Stream()
@@ -298,12 +309,12 @@ class FullPipe:
         """Results of `passes` decodes of the file's chunks (one call: consecutive batches
         through the engine's batch pipeline when passes > 1), chunk order, pass after pass."""
         if passes == 1:
-            return self.rec.decode_device(self.d_audio.data_ptr(), self.c_off, self.c_len,
+            return self.rec.decode_device(self.d_decode.data_ptr(), self.c_decode_off, self.c_len,
                                           beam=self.beam, stream=stream)
         n = len(self.c_len)
         if n == 0:  # more ranks than chunks
             return []
-        return self.rec.decode_device_batches(self.d_audio.data_ptr(), self.c_off * passes,
+        return self.rec.decode_device_batches(self.d_decode.data_ptr(), self.c_decode_off * passes,
                                               self.c_len * passes, [n] * passes,
                                               beam=self.beam, stream=stream)
 
